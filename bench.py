@@ -1,6 +1,6 @@
 """Benchmark of the FrozenBiLM masked-LM fwd+bwd hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 without a launcher: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one optimizer step of `main.train_one_epoch`'s body on a synthetic WebVid-shape batch already resident in
@@ -25,6 +25,12 @@ Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
                   fwd+bwd, threads = physical cores), rank 0, N=1 only.
   eval_forward -- the eval-mode forward alone (north_star's ">= 40 % of peak on the fused forward"), timed in the same run.
   host         -- host cost of enqueueing one step, measured where the GPU cannot hide it (same launch sequence at B=1).
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed, in float32 (write_outputs): DIR/loss.npy,
+DIR/grads.npy and DIR/params.npy (the trainable parameters' gradients and their values after the Adam update, concatenated in
+model.parameters() order), DIR/logits.npy with --full-logits; an eval-forward run writes loss.npy only.  Arrays larger than 4 Mi
+elements are written as a fixed, seeded sample of their elements (at most 64 MB in all).  The inputs, the weights and the dropout
+masks are seeded, so two builds run with the same arguments can be compared output for output.
 
 At --gpus 1 without a launcher the measurement runs in a child process (supervise_single_rank): if that process dies before
 it printed its line (a signal, not a Python exception) it is started once more and the line says `"attempts": 2`; `--no-retry`
@@ -84,6 +90,24 @@ def synth_batch(B, T, F, L, V, seed, device):
 
 
 PREWARM_STEPS = 12
+DUMP_MAX_ELEMENTS = 4 << 20  # per array written by --dump-outputs: 16 MB in float32, so the four arrays of a step stay under 64 MB
+
+
+def write_outputs(dirpath, arrays, max_elements=DUMP_MAX_ELEMENTS, seed=0):
+    """--dump-outputs: every tensor of `arrays` as <dirpath>/<name>.npy in float32.  A tensor of more than `max_elements` elements
+    is written as a sample of its flattened elements: `max_elements` positions drawn (with repetition) from a CPU generator seeded
+    with `seed`, in ascending order.  The positions depend only on the tensor's size, so every run and every build picks the same
+    elements, and tensors of one size (grads and params) are sampled at the same positions."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > max_elements:
+            g = torch.Generator().manual_seed(seed)
+            idx = torch.randint(t.numel(), (max_elements,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirpath, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -123,7 +147,13 @@ def main():
     ap.add_argument("--workload", default="mlm", choices=["mlm", "videoqa", "mc"],
                     help="mlm = BASELINE configs[1] (the headline); videoqa = configs[3] (zero-shot open-ended eval loop, "
                          "n_ans=1000); mc = configs[4] (4-way multiple choice, B=8, S=512)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "mlm":
+        ap.error("--dump-outputs writes the outputs of the mlm step only")
     if _wants_supervisor(args):
         sys.exit(supervise_single_rank())
     import faulthandler
@@ -189,10 +219,15 @@ def main():
     batch = synth_batch(B, T, F, Lt, cfg.vocab_size, seed=1 + rank, device=dev)
     t_build = time.time() - t_build
 
-    def step(full_logits=args.full_logits):
+    kept = {}  # --dump-outputs: the output mapping of the last timed step (kept from that step only: peak memory stays as it was)
+
+    def step(full_logits=args.full_logits, keep=False):
         if args.eval_forward:
             with torch.no_grad():
-                return model(**batch).loss
+                out = model(**batch)
+            if keep:
+                kept["out"] = out
+            return out.loss
         opt.zero_grad(set_to_none=False)
         out = model(**batch)
         loss = out.loss
@@ -200,6 +235,8 @@ def main():
             out.logits  # materialises the [B,S,V] tensor (filled on first access)
         loss.backward()
         opt.step(clip_max_norm=0.1)
+        if keep:
+            kept["out"] = out
         return loss
 
     def sync():
@@ -220,9 +257,10 @@ def main():
     t0 = time.time()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     host_marks = []
+    keep_at = args.steps - 1 if args.dump_outputs else -1
     marks[0].record()
     for i in range(args.steps):
-        loss = step()
+        loss = step(keep=i == keep_at)
         marks[i + 1].record()
         host_marks.append(time.time())
     t_host = time.time() - t0  # host time of the loop (it blocks once per step, on the label-row count at the start of forward)
@@ -238,6 +276,20 @@ def main():
     step_ms_host = [round((b - a) * 1e3, 2) for a, b in zip([t0] + host_marks[:-1], host_marks)]
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
+    if args.dump_outputs:  # before the legs below run more steps on the model
+        _phase("dump outputs")
+        out = kept.pop("out")
+        if rank == 0:
+            arrays = {"loss": out.loss}
+            if not args.eval_forward:
+                trainable = [p for p in model.parameters() if p.requires_grad]
+                arrays["grads"] = torch.cat([p.grad.reshape(-1) for p in trainable])
+                arrays["params"] = torch.cat([p.detach().reshape(-1) for p in trainable])
+                if args.full_logits:
+                    arrays["logits"] = out.logits
+            write_outputs(args.dump_outputs, arrays)
+            del arrays
+        del out
 
     S = T + Lt
     fwd_f, bwd_f = algorithmic_flops_per_sample(S=S)

@@ -291,3 +291,24 @@ def test_bench_supervisor_takes_the_measuring_process_with_it(tmp_path):
                 alive = False
             time.sleep(0.05)
         assert not alive, f"the measuring process survived its supervisor's {sig.name}"
+
+
+def test_bench_write_outputs_float32_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files; a large tensor is sampled at positions that depend on its size only (so two
+    builds, and grads / params of one step, are compared element for element); the four arrays of a step stay under 64 MB."""
+    import bench
+
+    big = torch.arange(1000, dtype=torch.float64)
+    arrays = {"loss": torch.tensor(1.5), "small": torch.arange(6.0).view(2, 3), "big": big, "twice": big * 2}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays, max_elements=64)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].shape == () and got["loss"] == 1.5
+    assert np.array_equal(got["small"], np.arange(6.0).reshape(2, 3))
+    pos = got["big"]  # the values of arange are their positions
+    assert pos.shape == (64,) and (np.diff(pos) >= 0).all() and pos.max() < 1000 and len(np.unique(pos)) > 32
+    assert np.array_equal(got["twice"], 2 * pos)
+    for n in arrays:
+        assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n])
+    assert (3 * bench.DUMP_MAX_ELEMENTS + 1) * 4 < 64e6  # loss, grads, params, logits
