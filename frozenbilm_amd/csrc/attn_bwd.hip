@@ -6,22 +6,21 @@
 //   dV = drop(P)^T.dO
 //   dQ = dS.K   + G1.PK,    G1[i,r] = sum_{j: idx(i-j)=r} dS[i,j]        (c2p)
 //   dK = dS^T.Q + G2.PQ,    G2[j,r] = sum_{i: idx(i-j)=r} dS[i,j]        (p2c)
-//   dPK = sum_b G1^T.Q ,  dPQ = sum_b G2^T.K     (per head; done by the GEMM kernel on G1^T/G2^T written here)
+//   dPK = sum_b G1^T.Q ,  dPQ = sum_b G2^T.K     (per head; pos_grad, straight from dS / dS^T)
 //
-// The launches of one layer execution (round 6; frozenbilm_amd/attn_bwd.py):
-//   attn_bwd_prep  D = rowdot(dO, O) and the position tables expanded by the index map, PQX / PKX[h][delta + Sp][d] = table[idx(delta)]
-//                  (only what the chosen route needs: the transposed copies K^T, Q^T, PK^T, PQ^T of rounds 1-5 on request).
+// The launches of one layer execution (frozenbilm_amd/attn_bwd.py).  Shipped route (the training forward saved P):
+//   attn_bwd_prep  D = rowdot(dO, O) and the position tables expanded by the index map, PQX / PKX[h][delta + Sp][d] = table[idx(delta)].
 //   attn_bwd_dspk  key-major: one workgroup per (b, h, 64-key tile) sweeps the query tiles; P from the probabilities the training
 //                  forward saved (dropout decision in their sign bit), dS, dV AND dK (dS^T.Q + the p2c term as a Toeplitz product of
 //                  a sheared LDS tile against PQX); writes dS and dS^T (bf16, zero where masked).
 //   attn_bwd_dq    query-major: reads dS, dQ = dS.K + the c2p term as a Toeplitz product against PKX.
 //   pos_grad       dPK / dPQ of ALL layer executions at the end of backward, straight from dS / dS^T (fbl_attn_pos_grad).
-// Earlier routes, kept behind engine options for A/B measurements and for calls without saved probabilities:
+// Recompute route (no saved probabilities): attn_bwd_prep (also Q^T, PQ^T) -> attn_bwd_ds -> attn_bwd_dq -> attn_bwd_shear -> pos_grad:
 //   attn_bwd_ds    kernel A that RECOMPUTES P exactly like the forward (row-tile split fp16 T1/T2 bias GEMMs + LDS gather, same
-//                  rounding) with the keys as lane columns; attn_bwd_dsp: kernel A from saved probabilities without dK.
-//   attn_bwd_shear<NEG> ("kernel BC"): one workgroup per (b, h, 32 rows): X_out = dSx.Y + G.Ptab with the scatter
-//                  G[row, idx(+-(row-col))] += dSx[row,col] done by LDS stores / atomics into a [32 x W] bf16 tile, W = the index
-//                  range the 32 rows can reach (~S+32 <= 512); optionally writes G^T for the position-table GEMMs of rounds 1-5.
+//                  rounding) with the keys as lane columns; dV, dS, dS^T.
+//   attn_bwd_shear key-major pass for dK: one workgroup per (b, h, 32 keys): dK = dS^T.Q + G2.PQ with the scatter
+//                  G2[key, idx(query-key)] += dS^T[key,query] done by LDS stores / atomics into a [32 x W] bf16 tile, W = the index
+//                  range the 32 keys can reach (~S+32 <= 512).
 #include "attn_common.h"
 #include "../../include/fbl.h"
 
@@ -56,18 +55,18 @@ __global__ void rowdot_kernel(const bf16* dO, const bf16* O, long ld, float* out
 }
 
 // ------------------------------------------------------------------------------------------- backward preparation
-// Everything the backward needs before kernel A as ONE launch instead of five: the position-contiguous copies K^T, Q^T
-// (head-major [nh,64,B,Sp]: operands of the shear passes and of the position-table gradient GEMMs), PK^T, PQ^T
-// ([nh,64,span2]) and D = rowdot(dO, O).  Five small kernels (two of them 1.5 MB each, i.e. pure launch latency) cannot
-// fill the chip one after the other; as block ranges of one grid they run side by side.
+// Everything the backward needs before kernel A as ONE launch: D = rowdot(dO, O), the index-expanded tables PQX / PKX and,
+// for the key-major shear pass of the recompute route, the position-contiguous copies Q^T (head-major [nh,64,B,Sp]) and PQ^T
+// ([nh,64,span2]).  Small kernels (pure launch latency) cannot fill the chip one after the other; as block ranges of one
+// grid they run side by side.
 struct PrepArgs {
-  const bf16* q; const bf16* k; long ldq;
+  const bf16* q; long ldq;
   const bf16* pq; const bf16* pk; long ldp;
   const bf16* dO; const bf16* O; long ldo;
-  bf16* QT; bf16* KT; bf16* PQT; bf16* PKT; float* Dv;
+  bf16* QT; bf16* PQT; float* Dv;
   int B, S, Sp, nh, span2;
-  int n_kt, n_qt, n_pkt, n_pqt;  // blocks of the K / Q transposes and of the PK / PQ table transposes (0: output not wanted)
-  const int32_t* row0;  // [B+1] packed-row layout of q / k / dO / O (see attn_fwd.hip) or null; the outputs keep [B, S(p)]
+  int n_qt, n_pqt;  // blocks of the Q transpose and of the PQ table transpose (0: output not wanted)
+  const int32_t* row0;  // [B+1] packed-row layout of q / dO / O (see attn_fwd.hip) or null; the outputs keep [B, S(p)]
   // tables expanded by the relative-index map (the fused key-/query-major passes): X[h][t][d] = tab[relidx[t - Sp + S - 1]][h*64 + d],
   // t in [0, 2 Sp) standing for delta = i - j = t - Sp (indices beyond the map's range are clamped: dS is zero there)
   const int16_t* relidx;
@@ -111,28 +110,24 @@ __device__ __forceinline__ void head_transpose_tile(uint32_t* tile, const bf16* 
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(PrepArgs a) {
   __shared__ uint32_t tile[64 * 33];
   int id = blockIdx.x;
-  if (id < a.n_kt + a.n_qt) {  // K^T (first n_kt blocks) and Q^T, head-major
-    const bool isq = id >= a.n_kt;
-    if (isq) id -= a.n_kt;
+  if (id < a.n_qt) {  // Q^T, head-major
     const int nst = a.Sp / 64;
     const int st = id % nst, h = (id / nst) % a.nh, b = id / (nst * a.nh);
     const long rb = a.row0 ? (long)a.row0[b] : (long)b * a.S;
     const int lim = a.row0 ? min(a.row0[b + 1] - a.row0[b], a.S) : a.S;  // (rows beyond it read as zero, like S <= s < Sp)
-    head_transpose_tile(tile, isq ? a.q : a.k, a.ldq, isq ? a.QT : a.KT, lim, a.Sp, 64l * a.B * a.Sp, a.Sp, (long)a.B * a.Sp,
+    head_transpose_tile(tile, a.q, a.ldq, a.QT, lim, a.Sp, 64l * a.B * a.Sp, a.Sp, (long)a.B * a.Sp,
                         st * 64, h, b, rb);
     return;
   }
-  id -= a.n_kt + a.n_qt;
-  if (id < a.n_pkt + a.n_pqt) {  // PK^T, PQ^T: [nh][64][span2]
-    const bool isq = id >= a.n_pkt;
-    if (isq) id -= a.n_pkt;
+  id -= a.n_qt;
+  if (id < a.n_pqt) {  // PQ^T: [nh][64][span2]
     const int nst = a.span2 / 64;
     const int st = id % nst, h = id / nst;
-    head_transpose_tile(tile, isq ? a.pq : a.pk, a.ldp, isq ? a.PQT : a.PKT, a.span2, a.span2, 64l * a.span2,
+    head_transpose_tile(tile, a.pq, a.ldp, a.PQT, a.span2, a.span2, 64l * a.span2,
                         (long)a.nh * 64 * a.span2, a.span2, st * 64, h, 0, 0);
     return;
   }
-  id -= a.n_pkt + a.n_pqt;
+  id -= a.n_pqt;
   if (id < a.n_pqx + a.n_pkx) {  // expanded tables [nh][2 Sp][64]: a row gather, 64 rows x one head per block
     const bool isk = id >= a.n_pqx;
     if (isk) id -= a.n_pqx;
@@ -493,12 +488,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_ds_kernel(BwdAArgs a) {
 
 // ------------------------------------------------------------------------------------------- kernel A, P saved by the forward
 // The training forward (attn_fwd.hip, SAVEP) leaves the un-normalised probabilities of every visited tile pair in HBM --
-// psave[b,h,i,j] = exp2(k2*(s_ij - m)), bf16, with m the running row maximum at key tile j/64 (msave) -- so this pass does
-// not repeat Q.K^T, the two bias GEMMs against the position-table windows and the LDS gather (kernel A above: 28 of its 44
-// MFMA pairs, ten fp16 tile stores, 32 element reads per lane and a barrier per tile pair; 288 GB of HBM hold the 157 MB
-// per layer execution easily):  P_ij = psave_ij * exp2(msave_i - lse_i*log2(e)).  Everything after P is kernel A's:
-// dP = dO.V^T through the dropout mask (the sign bits of psave), dS = P*(dP - D)*scale, dV += drop(P)^T.dO, dS and dS^T staged through
-// LDS.  Two barriers per tile pair, 37 KiB of LDS, no index table, no position tables.
+// psave[b,h,i,j] = exp2(k2*(s_ij - m)), bf16, with m the running row maximum at key tile j/64 (msave) -- so the shipped kernel A
+// (attn_bwd_dspk below) does not repeat Q.K^T, the two bias GEMMs against the position-table windows and the LDS gather
+// (kernel A above: 28 of its 44 MFMA pairs, ten fp16 tile stores, 32 element reads per lane and a barrier per tile pair; 288 GB
+// of HBM hold the 157 MB per layer execution easily):  P_ij = psave_ij * exp2(msave_i - lse_i*log2(e)).
 struct BwdPArgs {
   const bf16* psave; const float* msave;
   const bf16* v; long ldv;
@@ -513,166 +506,12 @@ struct BwdPArgs {
 };
 constexpr int LDP = 80;                     // bf16 row stride of the P tile: 40 dwords = 8 x odd -> the eight consecutive rows a
                                             // ds_read_b64_tr_b16 pass touches (lanes 0-31: 32 bytes each) tile the 64 banks
-constexpr int P_DOS = 0;                    // [64 i][64] bf16 swizzled
-constexpr int P_PS = P_DOS + 8192;          // [64 i][LDP] bf16
-constexpr int P_ST = P_PS + 64 * LDP * 2;   // dS staging [64 i][LDV]
-constexpr int P_STT = P_ST + 64 * LDV * 2;  // dS^T staging [64 j][LDV]
-constexpr int P_ROW = P_STT + 64 * LDV * 2; // float f[64], D[64]
-constexpr int P_TOTAL = P_ROW + 512;
-
-struct PTileRegs {
-  bf16x8 d[2], p[2];
-  float f, D;
-};
-
-template <bool PACKED = false>
-__global__ __launch_bounds__(256, 3) void attn_bwd_dsp_kernel(BwdPArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 15, g = lane >> 4;
-  const int S = a.S, Sp = a.Sp;
-  const WgCoord wc = wg_coord(Sp / 64, a.nh, a.B, a.border);
-  const int j0 = wc.x * 64, h = wc.h, b = wc.b;
-  const int j = j0 + w * 16 + c;  // this lane's key
-  const long rb = PACKED ? (long)a.row0[b] : (long)b * S;
-  const int lim = PACKED ? min(a.row0[b + 1] - a.row0[b], S) : S;
-  const int jc = min(j, lim - 1);
-  float* rF = (float*)(smem + P_ROW);
-  float* rD = rF + 64;
-  bf16* dst = (bf16*)(smem + P_ST);    // dS tile [query][key]
-  bf16* dstT = (bf16*)(smem + P_STT);  // dS^T tile [key][query]
-
-  const int kl = a.klen ? min(a.klen[b], S) : S;
-  const int nqt = (j0 < kl) ? (kl + 63) / 64 : 0;
-  const int srow = tid >> 3, sch = tid & 7;
-  const int fb0 = c * 128 + ((g ^ (c & 7)) << 4), fb1 = fb0 ^ 64;  // dO fragment of row x*16 + c: + x*2048
-  const int sb = srow * 128 + ((sch ^ (srow & 7)) << 4);           // dO staging slot of row srow + 32 t: + t*4096
-  const int sp = srow * (LDP * 2) + sch * 16;                      // P staging slot: + t*32*LDP*2
-
-  bf16x8 vf[2];
-  {
-    const long off = (rb + jc) * a.ldv + h * 64 + g * 8;
-    vf[0] = *(const bf16x8*)(a.v + off);
-    vf[1] = *(const bf16x8*)(a.v + off + 32);
-  }
-  f32x4 dv[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) dv[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const DropKey dk = attn_drop_key(a.p_drop > 0.f ? fbl_seed(a.seed, a.seed_dev) : 0, b * a.nh + h, a.p_drop);
-  const long sbase = ((long)b * a.nh + h) * Sp * Sp;
-  const float* mrow = a.msave + (((long)b * a.nh + h) * (Sp >> 6) + wc.x) * S;
-
-  auto load_tile = [&](int it, PTileRegs& R) {
-    const int i0 = it * 64;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int il = i0 + srow + t * 32;
-      R.d[t] = *(const bf16x8*)(a.dO + (rb + min(il, lim - 1)) * a.ldo + h * 64 + sch * 8);
-      R.p[t] = *(const bf16x8*)(a.psave + sbase + (long)il * Sp + j0 + sch * 8);
-    }
-    R.f = 0.f; R.D = 0.f;  // padding and masked queries: lse = +inf in the forward -> P = 0
-    if (tid < 64) {
-      const int i = i0 + tid;
-      if (i < lim) {
-        const long o = ((long)b * a.nh + h) * S + i;
-        const float l = a.lse[o];
-        R.f = (l < INFINITY) ? __builtin_amdgcn_exp2f(mrow[i] - l * LOG2E) : 0.f;
-        R.D = a.Dv[o];
-      }
-    }
-  };
-  auto store_tile = [&](const PTileRegs& R) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      *(bf16x8*)(smem + P_DOS + sb + t * 4096) = R.d[t];
-      *(bf16x8*)(smem + P_PS + sp + t * (32 * LDP * 2)) = R.p[t];
-    }
-    if (tid < 64) {
-      rF[tid] = R.f;
-      rD[tid] = R.D;
-    }
-  };
-
-  PTileRegs R;
-  if (nqt > 0) load_tile(0, R);
-  for (int it = 0; it < nqt; ++it) {
-    const int i0 = it * 64;
-    store_tile(R);
-    __syncthreads();  // (also: every wave is done with the staging tiles of the previous pair)
-    if (it + 1 < nqt) load_tile(it + 1, R);  // the next pair's operands fly during this pair's arithmetic
-
-    bf16x4 dsb[4], pfh[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      // P~ of queries nt*16 + g*4 + {0..3}, key column c: the transposing read hands each lane its column of a [4 x 16] block
-      union { tr16x4 t; bf16x4 v; } pu;
-      pu.t = lds_tr16((const bf16*)(smem + P_PS + (nt * 16 + g * 4 + (c >> 2)) * (LDP * 2) + (w * 16 + (c & 3) * 4) * 2));
-      const f32x4 f4 = *(const f32x4*)(rF + nt * 16 + g * 4);
-      const f32x4 d4 = *(const f32x4*)(rD + nt * 16 + g * 4);
-      f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)(smem + P_DOS + nt * 2048 + fb0), vf[0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)(smem + P_DOS + nt * 2048 + fb1), vf[1], acc, 0, 0, 0);
-      // the forward left the dropout decision in the sign bit of the saved probability (P >= 0: set = dropped)
-      float keep[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) keep[r] = pu.t[r] < 0 ? 0.f : dk.inv_keep;  // (the 16-bit pattern as a signed integer)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pv = f4[r] != 0.f ? fabsf(bf2f(pu.v[r])) * f4[r] : 0.f;  // (f = 0 rows may hold garbage in psave)
-        dsb[nt][r] = f2bf(pv * (acc[r] * keep[r] - d4[r]) * a.scale);
-        pfh[nt][r] = f2bf(pv * keep[r]);
-      }
-    }
-    // ---- dV^T += dO^T . drop(P):  k-slot e of step kk <-> query kk*32 + (e>>2)*16 + g*4 + (e&3)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 pf;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        pf[e] = pfh[2 * kk][e];
-        pf[4 + e] = pfh[2 * kk + 1][e];
-      }
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int r = g * 4 + (c >> 2);
-        const int ch = dt * 2 + ((c >> 1) & 1), sub = (c & 1) * 8;
-        const char* db = smem + P_DOS + r * 128 + ((ch ^ (r & 7)) << 4) + sub;
-        union { tr16x4 h[2]; bf16x8 v; } u;
-        u.h[0] = lds_tr16((const bf16*)(db + kk * 4096));
-        u.h[1] = lds_tr16((const bf16*)(db + kk * 4096 + 2048));
-        dv[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(u.v, pf, dv[dt], 0, 0, 0);
-      }
-    }
-    // ---- dS and dS^T leave through LDS transposes: 16-byte rows
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      *(bf16x4*)(dstT + (w * 16 + c) * LDV + nt * 16 + g * 4) = dsb[nt];  // [key][query]
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dst[(nt * 16 + g * 4 + r) * LDV + w * 16 + c] = dsb[nt][r];  // [query][key]
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int row = srow + t * 32;
-      *(bf16x8*)(a.dS + sbase + (long)(i0 + row) * Sp + j0 + sch * 8) = *(const bf16x8*)(dst + row * LDV + sch * 8);
-      *(bf16x8*)(a.dST + sbase + (long)(j0 + row) * Sp + i0 + sch * 8) = *(const bf16x8*)(dstT + row * LDV + sch * 8);
-    }
-  }
-
-  if (j < lim) {
-    bf16* op = a.dV + (rb + j) * a.lddv + h * 64 + g * 4;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      *(bf16x4*)(op + dt * 16) = (bf16x4){f2bf(dv[dt][0]), f2bf(dv[dt][1]), f2bf(dv[dt][2]), f2bf(dv[dt][3])};
-  }
-}
 
 // ------------------------------------------------------------------------------------------- kernel A + the key-major shear pass
-// attn_bwd_dsp with dK formed in place (round 6): the workgroup of a 64-key tile already holds every dS[i, j] of its keys, one
+// Kernel A from saved P with dK formed in place (round 6): the workgroup of a 64-key tile already holds every dS[i, j] of its keys, one
 // query tile at a time, so both terms of
 //     dK_j = sum_i dS[i,j] Q_i  +  sum_i dS[i,j] PQ[idx(i-j)]
-// are accumulated next to dV instead of by a second kernel that reads dS^T back (attn_bwd_shear<NEG = 1>: 78 us and 157 MB per
+// are accumulated next to dV instead of by a second kernel that reads dS^T back (attn_bwd_shear: 78 us and 157 MB per
 // layer execution at the bench shape):
 //  * dK^T += Q^T . dS: the dS values are MFMA B operands exactly as they sit in the accumulator layout (like drop(P) for dV), the
 //    Q^T fragments are transposing reads of a row-major Q tile staged beside the dO tile;
@@ -940,7 +779,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dspk_kernel(BwdPKArgs ka) {
 }
 
 // ------------------------------------------------------------------------------------------- query-major pass (Toeplitz form)
-// dQ_i = sum_j dS[i,j] K_j + sum_j dS[i,j] PK[idx(i-j)]  from the dS tensor kernel A wrote -- what attn_bwd_shear<NEG = 0> computes by
+// dQ_i = sum_j dS[i,j] K_j + sum_j dS[i,j] PK[idx(i-j)]  from the dS tensor kernel A wrote -- what the scatter-based query-major shear pass of rounds 1-5 computed by
 // scattering dS into index space (LDS stores / atomics per element, an index table, a table GEMM over the whole window): here, like
 // the key-major half inside attn_bwd_dspk, the position term is a Toeplitz product against PKX (the table expanded by the index
 // map): the 64 x 64 dS tile of a pair is stored twice by the wave that owns its rows -- row-major (MFMA B fragments of dS.K) and
@@ -1075,51 +914,27 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(BwdQArgs a) {
   }
 }
 
-// ------------------------------------------------------------------------------------------- kernel BC
+// ------------------------------------------------------------------------------------------- key-major shear pass
 struct ShearArgs {
-  const bf16* X;                          // dS (NEG=0) or dS^T (NEG=1): [B,nh,Sp,Sp], rows = output rows
-  const bf16* YT; long y_sh, y_sb, y_sd;  // transposed K (NEG=0) / Q (NEG=1): index h*sh + b*sb + d*sd + s
-  const bf16* PT;                         // transposed position table [nh][64][span2]
+  const bf16* X;                          // dS^T: [B,nh,Sp,Sp], rows = output rows (keys)
+  const bf16* YT; long y_sh, y_sb, y_sd;  // transposed Q: index h*sh + b*sb + d*sd + s
+  const bf16* PT;                         // transposed position table PQ^T [nh][64][span2]
   const int16_t* relidx;
   const int32_t* klen;
   const int32_t* border;
-  bf16* out; long ldout;                  // row-major, head h at col h*64
-  bf16* GT;                               // [nh][B][Sp/32][rcnt][32]
+  bf16* out; long ldout;                  // dK, row-major, head h at col h*64
   int B, S, Sp, nh, span2, Wg;            // Wg: columns of the G tile (multiple of 32)
-  int rmin, rcnt;                         // only rows [rmin, rmin+rcnt) of G^T can be non-zero (range of relidx)
   int lin;                                // |delta| < lin: idx(delta) is injective (identity buckets) -> plain stores
-  const int32_t* row0;                    // [B+1] packed-row layout of `out` (PACKED kernels; see attn_fwd.hip) or null
-  const uint32_t* tilemask;               // [B][Sp/64] (fbl_gt_tilemask) or null: bit t set <=> rows [128t, 128t+128) of the rcnt
-                                          // G^T rows can be non-zero in this 64-row k-step; other rows are NOT written (nor read)
+  const int32_t* row0;                    // [B+1] packed-row layout of `out` (PACKED kernel; see attn_fwd.hip) or null
 };
-// rows [rbase, rbase + nks*32) of the position tables that the 32 output rows r0.. of a sample with kl valid positions reach
-__device__ __forceinline__ void gt_window(const int16_t* relidx, int S, int kl, int r0, bool neg, int Wg, int* rbase, int* nks) {
+// rows [rbase, rbase + nks*32) of the position table that the 32 output rows r0.. of a sample with kl valid positions reach
+__device__ __forceinline__ void gt_window(const int16_t* relidx, int S, int kl, int r0, int Wg, int* rbase, int* nks) {
   const int hi = 2 * S - 2;
-  const int dlo = neg ? -(r0 + 31) : r0 - (kl - 1);
-  const int dhi = neg ? (kl - 1 - r0) : (r0 + 31);
+  const int dlo = -(r0 + 31), dhi = kl - 1 - r0;
   const int rb = (int)relidx[min(max(dlo + S - 1, 0), hi)] & ~7;
   const int rt = (int)relidx[min(max(dhi + S - 1, 0), hi)];
   *rbase = rb;
   *nks = min((rt - rb + 32) / 32, Wg / 32);
-}
-// one thread per (sample, 64-row k-step): which 128-row tiles of the rcnt G^T rows the step's two 32-row blocks can touch
-__global__ void gt_tilemask_kernel(const int16_t* relidx, const int32_t* klen, int B, int S, int Sp, int neg, int rmin, int rcnt,
-                                   int Wg, uint32_t* mask) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int steps = Sp / 64;
-  if (t >= B * steps) return;
-  const int b = t / steps, j = t - b * steps;
-  const int kl = klen ? min(klen[b], S) : S;
-  uint32_t m = 0;
-  for (int half = 0; half < 2; ++half) {
-    const int r0 = (2 * j + half) * 32;
-    if (r0 >= kl) continue;
-    int rbase, nks;
-    gt_window(relidx, S, kl, r0, neg != 0, Wg, &rbase, &nks);
-    const int lo = max(rbase - rmin, 0), hi = min(rbase + nks * 32 - rmin, rcnt);
-    for (int tt = lo / 128; tt * 128 < hi; ++tt) m |= 1u << tt;
-  }
-  mask[t] = m;
 }
 constexpr int C_IDX = 0;           // int16[1024]: relative-index table padded to the tile grid
 constexpr int C_G = C_IDX + 2048;  // [32][Wg + 8] bf16
@@ -1130,38 +945,26 @@ constexpr int C_G = C_IDX + 2048;  // [32][Wg + 8] bf16
 //  * each wave scatters only into its own 16 rows of G.  A 16x64 patch that lies entirely in the identity-bucket band
 //    (|i-j| < lin, idx = delta + idx(0)) needs no table lookup and no atomics: one unconditional LDS store per element
 //    (zeros of padded / masked positions are diverted to the row's padding slot);
-//  * the table GEMM walks only the index range the valid columns [0, klen) can reach, and G^T leaves through the
-//    matrix cores: D = G_frag . I puts 4 consecutive rows of one table index in a lane (an exact transpose of the bf16
-//    values), so there is no column-wise LDS read-out.
-template <bool NEG, bool PACKED = false>
+//  * the table GEMM walks only the index range the valid columns [0, klen) can reach.
+template <bool PACKED = false>
 __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, g = lane >> 4;
-  const int S = a.S, Sp = a.Sp, hi = 2 * S - 2;
+  const int S = a.S, Sp = a.Sp;
   const WgCoord wc = wg_coord(Sp / 32, a.nh, a.B, a.border);
-  const int bx = wc.x, r0 = bx * 32, h = wc.h, b = wc.b;
+  const int r0 = wc.x * 32, h = wc.h, b = wc.b;
   const int LDG = a.Wg + 8;  // bf16 elements; rows stay 16-byte aligned, 8 padding slots per row
   const int rl = w * 16 + c;  // local row
   const int row = r0 + rl;
   bf16* G = (bf16*)(smem + C_G);
   int16_t* idx = (int16_t*)(smem + C_IDX);
-  const bool wgt = a.GT != nullptr;  // G^T wanted (the per-head position-table GEMMs of rounds 1-5; fbl_attn_pos_grad reads dS itself)
-  bf16* gt = a.GT + ((((long)h * a.B + b) * (Sp / 32) + bx) * a.rcnt) * 32;
   const bf16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
   const int kl = a.klen ? min(a.klen[b], S) : S;
   const long rb = PACKED ? (long)a.row0[b] : (long)b * S;                  // first output row of this sample
   const int lim = PACKED ? min(a.row0[b + 1] - a.row0[b], S) : S;          // output rows that exist
-  if (r0 >= kl) {  // rows entirely beyond the sample's last valid position: dS is zero -> zero output rows, zero G^T block
-    // The consumer of G^T (the position-table GEMMs) skips a 64-wide k-step whose first row is beyond kl, so this block
-    // only has to exist (as zeros) when it is the odd half of a step whose even half is valid.
-    if (wgt && (bx & 1) && (r0 - 32 < kl)) {
-      const uint32_t tm = a.tilemask ? a.tilemask[b * (Sp / 64) + (bx >> 1)] : ~0u;
-      if (!(FBL_ATTN_DBGBITS & 64))
-        for (int id = tid; id < a.rcnt * 4; id += 128)
-          if ((tm >> (id >> 9)) & 1) *(bf16x8*)(gt + (long)id * 8) = z8;  // (id >> 2 = row, 128 rows per tile)
-    }
+  if (r0 >= kl) {  // rows entirely beyond the sample's last valid position: dS is zero -> zero output rows
     if (row < lim) {
       bf16* op = a.out + (rb + row) * a.ldout + h * 64 + g * 4;
 #pragma unroll
@@ -1172,21 +975,13 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
   // table rows reachable from these 32 rows x the valid columns [0, kl): [rbase, rbase + nks*32); rbase aligned down to 8 so the
   // PT fragments stay 16-byte aligned.  dS is only defined (and non-zero) inside [kl x kl].
   int rbase, nks;
-  gt_window(a.relidx, S, kl, r0, NEG, a.Wg, &rbase, &nks);
-  (void)hi;
+  gt_window(a.relidx, S, kl, r0, a.Wg, &rbase, &nks);
   const int izero = (int)a.relidx[S - 1];  // idx(0)
   {
     const int vpr = nks * 4;  // 16-byte vectors per row
     for (int t = tid; t < 32 * vpr; t += 128) *(bf16x8*)(G + (t / vpr) * LDG + (t % vpr) * 8) = z8;
   }
   attn::load_idx_padded(idx, a.relidx, S, Sp, tid, 128);
-  // G^T rows outside [rbase, rbase + nks*32) are zero: written straight from here -- only inside the 128-row tiles that the
-  // consumer fetches for this 64-row k-step (tilemask: the tiles either of its two blocks can touch)
-  const uint32_t tmask = a.tilemask ? a.tilemask[b * (Sp / 64) + (bx >> 1)] : ~0u;
-  for (int id = tid; wgt && id < a.rcnt * 4; id += 128) {
-    const int r = a.rmin + (id >> 2);
-    if (!(FBL_ATTN_DBGBITS & 64) && ((tmask >> (id >> 9)) & 1) && (r < rbase || r >= rbase + nks * 32)) *(bf16x8*)(gt + (long)id * 8) = z8;
-  }
   const long xbase = (((long)b * a.nh + h) * Sp + row) * Sp;
   f32x4 acc[4];
 #pragma unroll
@@ -1195,12 +990,12 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
 
   const int nct = (kl + 63) / 64;
   const bf16* ytb = a.YT + h * a.y_sh + b * a.y_sb + (long)c * a.y_sd + g * 8;
-  const int16_t* ib = idx + (NEG ? (Sp - 1 - row + g * 8) : (Sp - 1 + row - g * 8));  // idx(delta) = ib[+-(col - g*8)]
+  const int16_t* ib = idx + (Sp - 1 - row + g * 8);  // idx(delta) = ib[col - g*8]
   bf16* grow = G + rl * LDG - rbase;  // indexed by the absolute table row
   const int wmax = rbase + nks * 32 - 1;
   const int dummy = rbase + a.Wg;      // the row's padding slots: never read
-  // lane-linear part of the identity-band slot: slot = izero + delta, delta = +-(row - col)
-  const int lin0 = izero + (NEG ? (g * 8 - row) : (row - g * 8));
+  // lane-linear part of the identity-band slot: slot = izero + delta, delta = col - row
+  const int lin0 = izero + g * 8 - row;
   const int rw = r0 + w * 16;
   struct Frags { bf16x8 y[8], x[2]; };
   auto load_ct = [&](int ct, Frags& F) {
@@ -1226,10 +1021,10 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
       const int cb = c0 + kk * 32;  // this lane's columns: cb + g*8 + e
       if (FBL_ATTN_DBGBITS & 512) continue;  // (debug builds: no scatter)
       if (band) {
-        const int s0 = NEG ? (lin0 + cb) : (lin0 - cb);
+        const int s0 = lin0 + cb;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const int slot = NEG ? (s0 + e) : (s0 - e);
+          const int slot = s0 + e;
           grow[bf2f(xv[e]) != 0.f ? slot : dummy] = xv[e];  // injective inside the band and G starts at 0: a plain store is exact
         }
       } else {
@@ -1237,8 +1032,8 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
         for (int e = 0; e < 8; ++e) {  // ~2/3 of dS is exactly 0 (padding / masks) and is skipped
           const float x = bf2f(xv[e]);
           if (x != 0.f) {
-            const int dlt = NEG ? (cb + g * 8 + e - row) : (row - cb - g * 8 - e);
-            const int gi = clampi((int)(NEG ? ib[cb + e] : ib[-(cb + e)]), rbase, wmax);
+            const int dlt = cb + g * 8 + e - row;
+            const int gi = clampi((int)ib[cb + e], rbase, wmax);
             // LDS atomics (packed bf16 add on the element's aligned pair, the other half adds 0) only where log buckets
             // can collide; a bucket collects a handful of terms, each partial sum rounded to bf16 like G itself is
             // before it meets the matrix cores
@@ -1264,15 +1059,8 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
       if (ct + 1 < nct) step(ct + 1, F1);
     }
   }
-  // ---- table part: acc[d][row] += sum_r PT[d][rbase + r] * G[row][r], PT fragments double-buffered from L2;
-  //      G^T[r][row] leaves via two identity MFMAs per 32 table rows
+  // ---- table part: acc[d][row] += sum_r PT[d][rbase + r] * G[row][r], PT fragments double-buffered from L2
   const bf16* pt = a.PT + (long)h * 64 * a.span2 + rbase + g * 8;
-  bf16x8 I0, I1;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    I0[e] = f2bf((g * 8 + e) == c ? 1.f : 0.f);
-    I1[e] = f2bf((g * 8 + e) == c + 16 ? 1.f : 0.f);
-  }
   auto load_pt = [&](int kk, bf16x8* dstf) {
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
@@ -1284,15 +1072,6 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
     const bf16x8 bfv = *(const bf16x8*)(G + rl * LDG + kk * 32 + g * 8);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[dt], bfv, acc[dt], 0, 0, 0);
-    if (!wgt) return;
-    const f32x4 zf = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 t0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfv, I0, zf, 0, 0, 0);  // [row g*4+j][table row kk*32 + c]
-    const f32x4 t1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfv, I1, zf, 0, 0, 0);  // [row g*4+j][table row kk*32+16+c]
-    const int ra = rbase + kk * 32 + c - a.rmin, rb = ra + 16;
-    if (ra >= 0 && ra < a.rcnt && !(FBL_ATTN_DBGBITS & 128))
-      *(bf16x4*)(gt + (long)ra * 32 + w * 16 + g * 4) = (bf16x4){f2bf(t0[0]), f2bf(t0[1]), f2bf(t0[2]), f2bf(t0[3])};
-    if (rb >= 0 && rb < a.rcnt && !(FBL_ATTN_DBGBITS & 128))
-      *(bf16x4*)(gt + (long)rb * 32 + w * 16 + g * 4) = (bf16x4){f2bf(t1[0]), f2bf(t1[1]), f2bf(t1[2]), f2bf(t1[3])};
   };
   // (a third k-step of fragments in flight, and 64-row workgroups of four waves, were measured: no gain / slower)
   bf16x8 pa[4], pb[4];
@@ -1317,7 +1096,7 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
 // dPQ[h][r][d] = sum_b sum_{(i,j): idx(i-j) = r} dS_b[i,j] K_b[j,d]        (NEG = 1: X = dS^T, Y = K, k index = key j)
 // of EVERY layer execution in one launch (autograd of model/deberta.py:870-918 through the c2p / p2c gathers), straight from
 // the dS / dS^T tensors kernel A wrote: until round 5 the shear passes wrote a sheared copy G^T of them (2 x 163 MB per layer
-// execution) that two batched split-K GEMMs fetched back at the end of backward (8 GB each way per step).  A table row r
+// execution) that two batched split-K GEMMs fetched back at the end of backward (8 GB each way per step; that route has been removed).  A table row r
 // collects the deltas [dlo[r], dlo[r] + dcnt[r]) (one inside the identity band, a few per log bucket; idx is monotone), so
 // with rows of X = dS (dS^T) staged in LDS the MFMA operand G[r][k] = sum_t X[k][k -+ (dlo[r] + t)] is a diagonal walk of
 // 16-bit reads -- 8 per fragment, against the 4 MFMAs it feeds.  One workgroup (4 waves) = one (execution, head, 256 table
@@ -1347,7 +1126,8 @@ __host__ __device__ constexpr int pg_pitch(int Sp) { return Sp + 2 * PG_PAD; }  
 __host__ __device__ constexpr int pg_buf(int Sp) { return 32 * pg_pitch(Sp) * 2 + 32 * PG_LDY * 2; }  // one staging buffer
 __host__ __device__ constexpr int pg_smem(int Sp) { return 2 * pg_buf(Sp); }
 
-// CM: upper bound of dcnt (deltas per table row): 3 covers S <= 300 at the DeBERTa-v2 bucket map, 8 every S <= 512
+// CM: upper bound of dcnt (deltas per table row): 3 or 8, chosen from dcnt_max by the launcher (the FrozenBiLM bucket map,
+// position_buckets 256 / max_relative_positions 512, peaks at 6 for S <= 512; maps beyond 8 are rejected)
 // NXR: 16-byte chunks of X per thread and block (Sp / 64); OCC: workgroups per CU the register budget is set for (3: one staging
 // buffer and two barriers per item, 2: two buffers and one barrier)
 template <bool NEG, int CM, int NXR, int OCC>
@@ -1508,12 +1288,6 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
 
 }  // namespace
 
-static inline int shear_wg(int S, int span2) {  // columns of the shear pass's G tile (a multiple of 32)
-  int Wg = S + 31 + 7;
-  if (Wg > span2) Wg = span2;
-  return (Wg + 31) / 32 * 32;
-}
-
 extern "C" int fbl_attn_rowdot(const void* dO, const void* O, int64_t ld, float* out, int B, int S, int nh,
                                void* stream) {
   if (ld % 8) return FBL_ERR_ALIGN;
@@ -1559,33 +1333,6 @@ extern "C" int fbl_disent_attn_bwd_ds(const void* q, const void* k, const void* 
     hipLaunchKernelGGL(attn_bwd_ds_kernel<true>, grid, dim3(256), smem_bytes, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(attn_bwd_ds_kernel<false>, grid, dim3(256), smem_bytes, (hipStream_t)stream, a);
-  FBL_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int fbl_disent_attn_bwd_dsp(const void* psave, const float* msave, const void* v, int64_t ldv, const void* dO,
-                                       int64_t ldo, const int32_t* klen, const int32_t* border, const float* lse, const float* Dv,
-                                       float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* dV, int64_t lddv,
-                                       void* dS, void* dST, int B, int S, int Sp, int nh, const int32_t* row0, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64) return FBL_ERR_SHAPE;
-  if ((ldv % 8) || (ldo % 8) || (lddv % 4)) return FBL_ERR_ALIGN;
-  if (!psave || !msave || !v || !dO || !lse || !Dv || !dV || !dS || !dST) return FBL_ERR_ARG;
-  if (row0 && !klen) return FBL_ERR_ARG;
-  if (B <= 0 || nh <= 0) return 0;
-  BwdPArgs a{(const bf16*)psave, msave, (const bf16*)v, ldv, (const bf16*)dO, ldo, klen, border, lse, Dv, scale, p_drop, seed,
-             seed_dev, (bf16*)dV, lddv, (bf16*)dS, (bf16*)dST, B, S, Sp, nh, row0};
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dsp_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, P_TOTAL);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dsp_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, P_TOTAL);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  const dim3 grid((unsigned)(Sp / 64) * nh * B);
-  if (row0)
-    hipLaunchKernelGGL(attn_bwd_dsp_kernel<true>, grid, dim3(256), P_TOTAL, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(attn_bwd_dsp_kernel<false>, grid, dim3(256), P_TOTAL, (hipStream_t)stream, a);
   FBL_CHECK_LAUNCH();
   return 0;
 }
@@ -1645,39 +1392,31 @@ extern "C" int fbl_disent_attn_bwd_dq(const void* dS, const void* k, int64_t ldk
   return 0;
 }
 
-extern "C" int fbl_disent_attn_bwd_shear(int neg, const void* X, const void* YT, int64_t y_sh, int64_t y_sb,
-                                         int64_t y_sd, const void* PT, const int16_t* relidx, const int32_t* klen,
-                                         const int32_t* border, void* out, int64_t ldout, void* GT, int gt_rmin, int gt_rcnt, int lin_span, int B, int S,
-                                         int Sp, int nh, int span2, const int32_t* row0, const uint32_t* gt_tilemask, void* stream) {
+extern "C" int fbl_disent_attn_bwd_shear(const void* dST, const void* QT, int64_t y_sh, int64_t y_sb, int64_t y_sd,
+                                         const void* PQT, const int16_t* relidx, const int32_t* klen, const int32_t* border,
+                                         void* dK, int64_t lddk, int lin_span, int B, int S, int Sp, int nh, int span2,
+                                         const int32_t* row0, void* stream) {
   if (S < 1 || S > 512 || Sp < S || Sp % 64 || span2 > 512 || span2 % 32) return FBL_ERR_SHAPE;
-  if ((ldout % 4) || (y_sd % 8) || (y_sb % 8) || (y_sh % 8)) return FBL_ERR_ALIGN;
+  if ((lddk % 4) || (y_sd % 8) || (y_sb % 8) || (y_sh % 8)) return FBL_ERR_ALIGN;
   if (B <= 0 || nh <= 0) return 0;
   // index range reachable from 32 consecutive rows: <= S + 31 entries (idx has slope <= 1), +7 for the 8-alignment
-  const int Wg = shear_wg(S, span2);
-  if (GT && (gt_rmin < 0 || gt_rcnt < 0 || gt_rmin + gt_rcnt > span2)) return FBL_ERR_ARG;
+  int Wg = S + 31 + 7;
+  if (Wg > span2) Wg = span2;
+  Wg = (Wg + 31) / 32 * 32;
   if (row0 && !klen) return FBL_ERR_ARG;
-  ShearArgs a{(const bf16*)X, (const bf16*)YT, y_sh, y_sb, y_sd, (const bf16*)PT, relidx, klen, border, (bf16*)out, ldout, (bf16*)GT,
-              B, S, Sp, nh, span2, Wg, gt_rmin, gt_rcnt, lin_span, row0, gt_tilemask};
+  ShearArgs a{(const bf16*)dST, (const bf16*)QT, y_sh, y_sb, y_sd, (const bf16*)PQT, relidx, klen, border, (bf16*)dK, lddk,
+              B, S, Sp, nh, span2, Wg, lin_span, row0};
   attn_debug_init();
   const int smem_bytes = C_G + 32 * (Wg + 8) * 2;
   static int attr_bytes = 0;
   if (smem_bytes > attr_bytes) {
-    hipError_t e1 = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    hipError_t e2 = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e1 != hipSuccess) return (int)e1;
-    if (e2 != hipSuccess) return (int)e2;
-    e1 = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    e2 = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e1 != hipSuccess) return (int)e1;
-    if (e2 != hipSuccess) return (int)e2;
+    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    if (e != hipSuccess) return (int)e;
     attr_bytes = smem_bytes;
   }
   dim3 grid((unsigned)(Sp / 32) * nh * B);
-  if (neg && row0)
-    hipLaunchKernelGGL((attn_bwd_shear_kernel<true, true>), grid, dim3(128), smem_bytes, (hipStream_t)stream, a);
-  else if (row0)
-    hipLaunchKernelGGL((attn_bwd_shear_kernel<false, true>), grid, dim3(128), smem_bytes, (hipStream_t)stream, a);
-  else if (neg)
+  if (row0)
     hipLaunchKernelGGL(attn_bwd_shear_kernel<true>, grid, dim3(128), smem_bytes, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(attn_bwd_shear_kernel<false>, grid, dim3(128), smem_bytes, (hipStream_t)stream, a);
@@ -1740,33 +1479,20 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
   return 0;
 }
 
-extern "C" int fbl_gt_tilemask(const int16_t* relidx, const int32_t* klen, int B, int S, int Sp, int span2, int neg, int gt_rmin,
-                               int gt_rcnt, uint32_t* mask, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64 || span2 > 512 || span2 % 32 || !relidx || !mask) return FBL_ERR_SHAPE;
-  if (gt_rmin < 0 || gt_rcnt < 0 || gt_rmin + gt_rcnt > span2 || gt_rcnt > 32 * 128) return FBL_ERR_ARG;
-  if (B <= 0) return 0;
-  const int n = B * (Sp / 64);
-  hipLaunchKernelGGL(gt_tilemask_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, relidx, klen, B, S, Sp, neg, gt_rmin,
-                     gt_rcnt, shear_wg(S, span2), mask);
-  FBL_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int fbl_attn_bwd_prep(const void* q, const void* k, int64_t ldq, const void* pq, const void* pk, int64_t ldp,
-                                 const void* dO, const void* O, int64_t ldo, void* QT, void* KT, void* PQT, void* PKT,
-                                 float* Dv, const int16_t* relidx, void* PQX, void* PKX, int B, int S, int Sp, int nh, int span2,
-                                 const int32_t* row0, void* stream) {
+extern "C" int fbl_attn_bwd_prep(const void* q, int64_t ldq, const void* pq, const void* pk, int64_t ldp, const void* dO,
+                                 const void* O, int64_t ldo, void* QT, void* PQT, float* Dv, const int16_t* relidx, void* PQX,
+                                 void* PKX, int B, int S, int Sp, int nh, int span2, const int32_t* row0, void* stream) {
   if (S < 1 || Sp < S || Sp % 64 || span2 <= 0 || span2 % 64) return FBL_ERR_SHAPE;
   if ((ldq % 8) || (ldp % 8) || (ldo % 8)) return FBL_ERR_ALIGN;
   if ((PQX || PKX) && !relidx) return FBL_ERR_ARG;
   if (!Dv) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
   const int n_tr = (Sp / 64) * nh * B, n_tab = (span2 / 64) * nh, n_x = (2 * Sp / 64) * nh;
-  PrepArgs a{(const bf16*)q, (const bf16*)k, ldq, (const bf16*)pq, (const bf16*)pk, ldp, (const bf16*)dO, (const bf16*)O, ldo,
-             (bf16*)QT, (bf16*)KT, (bf16*)PQT, (bf16*)PKT, Dv, B, S, Sp, nh, span2, KT ? n_tr : 0, QT ? n_tr : 0, PKT ? n_tab : 0,
-             PQT ? n_tab : 0, row0, relidx, (bf16*)PQX, (bf16*)PKX, PQX ? n_x : 0, PKX ? n_x : 0};
+  PrepArgs a{(const bf16*)q, ldq, (const bf16*)pq, (const bf16*)pk, ldp, (const bf16*)dO, (const bf16*)O, ldo, (bf16*)QT,
+             (bf16*)PQT, Dv, B, S, Sp, nh, span2, QT ? n_tr : 0, PQT ? n_tab : 0, row0, relidx, (bf16*)PQX, (bf16*)PKX,
+             PQX ? n_x : 0, PKX ? n_x : 0};
   const long n_dot = ((long)B * S * nh * 8 + 255) / 256;
-  const long grid = (long)a.n_kt + a.n_qt + a.n_pkt + a.n_pqt + a.n_pqx + a.n_pkx + n_dot;
+  const long grid = (long)a.n_qt + a.n_pqt + a.n_pqx + a.n_pkx + n_dot;
   hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
   FBL_CHECK_LAUNCH();
   return 0;

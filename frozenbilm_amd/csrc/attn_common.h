@@ -41,7 +41,7 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v,
 struct WgCoord { int x, h, b; };
 #ifdef FBL_DEBUG_SWITCHES
 __device__ int g_attn_plainmap;  // measurement switch (debug builds only): 1 = plain b-major mapping
-__device__ int g_attn_dbgbits;   // FBL_ATTN_DBG (backward kernels: 64 = no zero fill of G^T, 128 = no G^T stores)
+__device__ int g_attn_dbgbits;   // FBL_ATTN_DBG: ablation bits of the attention kernels (tools/README.md, bench_attn.py)
 #define FBL_ATTN_PLAINMAP g_attn_plainmap
 #define FBL_ATTN_DBGBITS g_attn_dbgbits
 static inline void attn_debug_init() {

@@ -443,17 +443,20 @@ extern "C" int fbl_disent_attn_fwd(const void* q, int64_t ldq, const void* k, in
   a.dbg = dbg;
   attn_debug_init();
   const int smem_bytes = sm_total(Sp);
-  // three workgroups per CU (<= 168 VGPRs), no register prefetch of the next key tile: the other two workgroups of the CU
-  // cover the load (measured 88.6 us vs 97.2 with the prefetch, whose registers spill)
-  static const int pf = FBL_ENV_INT("FBL_ATTN_PF", 1);  // (measurement builds) register prefetch of the next key tile
+  // three workgroups per CU (<= 168 VGPRs) AND a register prefetch of the next key tile, in flight during the gather / softmax /
+  // P.V phase: 98 -> 96.6 us alone (an earlier prefetching version lost, 97.2 vs 88.6 us, because its registers spilled; this
+  // one has no spills).  The kernels without the prefetch exist in the measurement build only (FBL_ATTN_PF=0).
   static int attr_bytes = 0;
   if (smem_bytes > attr_bytes) {
-    const void* fns[8] = {(const void*)attn_fwd_kernel<3, false>, (const void*)attn_fwd_kernel<3, false, true>,
-                          (const void*)attn_fwd_kernel<3, false, false, true>, (const void*)attn_fwd_kernel<3, false, true, true>,
-                          (const void*)attn_fwd_kernel<3, true>, (const void*)attn_fwd_kernel<3, true, true>,
-                          (const void*)attn_fwd_kernel<3, true, false, true>, (const void*)attn_fwd_kernel<3, true, true, true>};
-    for (int f = 0; f < 8; ++f) {
-      hipError_t e = hipFuncSetAttribute(fns[f], hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    const void* fns[] = {(const void*)attn_fwd_kernel<3, true>, (const void*)attn_fwd_kernel<3, true, true>,
+                         (const void*)attn_fwd_kernel<3, true, false, true>, (const void*)attn_fwd_kernel<3, true, true, true>,
+#ifdef FBL_DEBUG_SWITCHES
+                         (const void*)attn_fwd_kernel<3, false>, (const void*)attn_fwd_kernel<3, false, true>,
+                         (const void*)attn_fwd_kernel<3, false, false, true>, (const void*)attn_fwd_kernel<3, false, true, true>,
+#endif
+    };
+    for (const void* fn : fns) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
       if (e != hipSuccess) return (int)e;
     }
     attr_bytes = smem_bytes;
@@ -470,8 +473,12 @@ extern "C" int fbl_disent_attn_fwd(const void* q, int64_t ldq, const void* k, in
     else                                                                                                                \
       hipLaunchKernelGGL((attn_fwd_kernel<3, PF_>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);               \
   } while (0)
-  if (pf) FBL_FWD_LAUNCH(true);
-  else FBL_FWD_LAUNCH(false);
+#ifdef FBL_DEBUG_SWITCHES
+  static const int pf = FBL_ENV_INT("FBL_ATTN_PF", 1);  // 0: no register prefetch of the next key tile
+  if (!pf) FBL_FWD_LAUNCH(false);
+  else
+#endif
+    FBL_FWD_LAUNCH(true);
 #undef FBL_FWD_LAUNCH
   FBL_CHECK_LAUNCH();
   return 0;

@@ -22,9 +22,6 @@ namespace {
 //   small: 128x128, 4 waves (2x2), MI=4  -> 69.6 KiB LDS, 2 workgroups/CU   (narrow / short GEMMs)
 //   big:   256x256, 8 waves (2x4), MI=8  -> 136 KiB LDS, 1 workgroup/CU     (1/3 fewer LDS bytes per MFMA)
 // (the large square-ish problems run the 8-phase kernel of gemm8.hip instead of the NW = 8 configuration)
-constexpr int KSKIP_MAX_STEPS = 2048;  // K-steps per split of a launch that skips zero blocks (LDS list of the valid ones)
-constexpr int KSKIP_SMEM_BYTES = 3 * (128 * BK * 2 + 64 * BK * 2) + KSKIP_MAX_STEPS * 2 + 16;
-
 template <int NW> struct TileCfg {
   static constexpr int BM = 32 * NW, BN = 32 * NW;
   static constexpr int TILE_BYTES = BM * BK * 2;
@@ -36,7 +33,7 @@ template <int NW> struct TileCfg {
 // MI_ = 7 with NW = 8 a 224x256 tile for shapes whose 256x256 grid leaves CUs idle (8512 rows = 38 x 224 exactly:
 // 228 tiles on 256 CUs for N = 1536 instead of 204 bigger ones).  LDS keeps the 32*NW-row A image; the unused rows are
 // simply not fetched.
-template <int NW, int ACT, int AUX, bool SPLITK, int SCHED = 0, int MI_ = NW, bool KSKIP = false>
+template <int NW, int ACT, int AUX, bool SPLITK, int SCHED = 0, int MI_ = NW>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(GemmArgs g) {
   using Cfg = TileCfg<NW>;
   constexpr int MI = MI_;           // 16-row MFMA tiles per wave along M; 4 tiles (64 cols) along N
@@ -56,28 +53,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(
   const int wm = wave / WC, wn = wave % WC;
 
   int tm, tn;
-  int by = blockIdx.y;
-  if constexpr (KSKIP) {
-    // The batched position-table products are a 2-D grid (few tiles x many (batch, K-slice) pairs): consecutive workgroups
-    // -- x fastest -- go round-robin to the 8 XCDs, which would put the row tiles of ONE pair on different XCDs, each
-    // fetching that pair's B operand (Q^T / K^T, 1.3 MB) into its own L2.  Re-deal: 8 pairs at a time, workgroup L of the
-    // group of 8 * tiles on XCD L % 8 takes pair L % 8, tile L / 8 -- all tiles of a pair share one L2.
-    const int gx = gridDim.x;
-    if ((gridDim.y & 7) == 0) {
-      const int lin = blockIdx.y * gx + blockIdx.x;
-      const int grp = lin / (8 * gx), r = lin - grp * 8 * gx;
-      by = grp * 8 + (r & 7);
-      tile_of_block(r >> 3, g.tiles_m, g.tiles_n, &tm, &tn);
-    } else {
-      tile_of_block(blockIdx.x, g.tiles_m, g.tiles_n, &tm, &tn);
-    }
-  } else {
-    tile_of_block(blockIdx.x, g.tiles_m, g.tiles_n, &tm, &tn);
-  }
+  tile_of_block(blockIdx.x, g.tiles_m, g.tiles_n, &tm, &tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
-  const int batch = by / g.splitk;
-  const int ks = by % g.splitk;
+  const int batch = blockIdx.y / g.splitk;
+  const int ks = blockIdx.y % g.splitk;
   const int nk_total = g.K / BK;
   const int per = (nk_total + g.splitk - 1) / g.splitk;
   const int kt0 = ks * per;
@@ -97,17 +77,16 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(
     const int row = (q * NW + wave) * 8 + lrow;
     const int am = min(m0 + row, g.M - 1);
     const int bn = min(n0 + row, g.N - 1);
-    a_src[q] = A + (long)am * g.lda + (g.a_kblk ? (long)(lchunk >> 2) * g.a_kblk + (lchunk & 3) * 8 : (long)lchunk * 8);
+    a_src[q] = A + (long)am * g.lda + lchunk * 8;
     b_src[q] = B + (long)bn * g.ldb + lchunk * 8;
   }
   auto issue = [&](int kt, int stage) {
     char* base = smem + stage * STAGE_BYTES;
     const long koff = (long)kt * BK;
-    const long koff_a = g.a_kblk ? (long)kt * 2 * g.a_kblk : koff;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int off = (q * NW + wave) * 1024;
-      if ((q * NW + wave) * 8 < BM) glds16(a_src[q] + koff_a, base + off);  // (always true for the square tiles)
+      if ((q * NW + wave) * 8 < BM) glds16(a_src[q] + koff, base + off);  // (always true for the square tiles)
       glds16(b_src[q] + koff, base + TILE_BYTES + off);
     }
   };
@@ -185,71 +164,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(
         bf16x8 af[MI], bfg[4];
         read_frags(base, s, af, bfg);
         mfma_block(af, bfg);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's fragment reads of the stage are complete
-    }
-    __builtin_amdgcn_s_barrier();  // all LDS tile reads retired before the epilogue reuses the memory
-  } else if constexpr (KSKIP) {
-    // K-steps whose operand block is known to be all zero (rows beyond a sample's last valid position in the G^T
-    // operand of the position-table gradients) are neither fetched nor multiplied.  The problem is a pure stream -- 332 x 64
-    // outputs against megabytes of G^T per (layer execution, head), N = 64 -- so what matters is how many bytes a workgroup
-    // keeps in flight: the valid K-steps are listed ONCE (wave 0, ballot compaction into LDS: no scalar table lookup in
-    // front of every request) and run through a ring of three 24 KiB stages (A 128 rows, B 64 rows: the clamped duplicate
-    // rows of a 128-row B image are not fetched) with counted vmcnt and one raw barrier per step, as in the SCHED 5 ring:
-    // two steps of operands in flight instead of one fetched behind a drained queue (round 4: 2-stage loop, __syncthreads
-    // per step, a dependent scalar load + division per step: 3.3 us per K-step).
-    constexpr int KS_STAGE = Cfg::TILE_BYTES + 64 * BK * 2;  // 16 KiB + 8 KiB
-    constexpr int KS_NS = 3;
-    int16_t* klist = (int16_t*)(smem + KS_NS * KS_STAGE);    // up to KSKIP_MAX_STEPS entries (host-checked)
-    int* kcount = (int*)(smem + KS_NS * KS_STAGE + KSKIP_MAX_STEPS * 2);
-    if (wave == 0) {
-      int cnt = 0;
-      for (int base = kt0; base < kt1; base += 64) {
-        const int kt = base + lane;
-        bool valid = false;
-        if (kt < kt1) {
-          const int b = kt / g.kskip_steps;
-          valid = (kt - b * g.kskip_steps) * BK < g.kskip_len[b];
-          // (the 128-row tile of A this workgroup owns is all zero -- and unwritten -- in k-steps whose mask bit is clear)
-          if (valid && g.kskip_tilemask) valid = (g.kskip_tilemask[kt] >> tm) & 1u;
-        }
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(valid);
-        if (valid) klist[cnt + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (int16_t)kt;
-        cnt += __builtin_popcountll(m);
-      }
-      if (lane == 0) *kcount = cnt;
-    }
-    __syncthreads();
-    const int nv = __builtin_amdgcn_readfirstlane(*kcount);
-    auto issue_ks = [&](int i, int slot) {
-      const int kt = __builtin_amdgcn_readfirstlane((int)klist[i]);
-      char* base = smem + slot * KS_STAGE;
-      const long koff = (long)kt * BK;
-      const long koff_a = g.a_kblk ? (long)kt * 2 * g.a_kblk : koff;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int off = (q * NW + wave) * 1024;
-        glds16(a_src[q] + koff_a, base + off);
-        if ((q * NW + wave) * 8 < 64) glds16(b_src[q] + koff, base + Cfg::TILE_BYTES + off);  // (q < 2: six requests per thread)
-      }
-    };
-#pragma unroll
-    for (int s_ = 0; s_ < KS_NS - 1; ++s_)
-      if (s_ < nv) issue_ks(s_, s_);
-    for (int i = 0; i < nv; ++i) {
-      if (i + 1 < nv) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (i + KS_NS - 1 < nv) issue_ks(i + KS_NS - 1, (i + KS_NS - 1) % KS_NS);
-      const char* base = smem + (i % KS_NS) * KS_STAGE;
-      if (n0 + wn * 64 < g.N) {  // (N = 64 here: the second column of waves only helps with the staging)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          bf16x8 af[MI], bfg[4];
-          read_frags(base, s, af, bfg);
-          mfma_block(af, bfg);
-        }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's fragment reads of the stage are complete
     }
@@ -478,11 +392,9 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
                         const void* aux, int64_t ld_aux, float* out_f32, void* out_bf16, void* out_pre_bf16,
                         int64_t ldc, int batch, int64_t strideA, int64_t strideB, int64_t strideC,
                         int64_t strideAux, int64_t strideBias, int splitk, float* splitk_ws,
-                        int64_t splitk_ws_floats, int64_t a_kblock_stride, const int32_t* kskip_len, int kskip_steps,
-                        float p_drop, uint64_t drop_seed, void* stream, int seg_n = 0, void* seg_out = nullptr,
-                        int64_t seg_ld = 0, int64_t drop_row0 = 0, void* aux_stream = nullptr,
-                        const TailArgs* tail = nullptr, const uint64_t* drop_seed_dev = nullptr,
-                        const uint32_t* kskip_tilemask = nullptr) {
+                        int64_t splitk_ws_floats, float p_drop, uint64_t drop_seed, void* stream, int seg_n = 0,
+                        void* seg_out = nullptr, int64_t seg_ld = 0, int64_t drop_row0 = 0, void* aux_stream = nullptr,
+                        const TailArgs* tail = nullptr, const uint64_t* drop_seed_dev = nullptr) {
   if (M <= 0 || N <= 0 || batch <= 0) return 0;
   if ((aux_kind == FBL_AUX_ADAPTER_TAIL) != (tail != nullptr)) return FBL_ERR_ARG;
   if (K <= 0 || (K % BK) != 0) return FBL_ERR_SHAPE;           // K must be a multiple of 64 (callers zero-pad)
@@ -511,10 +423,6 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
   g.k8_per = 0;
   g.ws = accumulate ? splitk_ws : nullptr;
   g.Nw = Nw;
-  g.a_kblk = a_kblock_stride;
-  g.kskip_len = kskip_len;
-  g.kskip_steps = kskip_steps;
-  g.kskip_tilemask = kskip_tilemask;
   g.drop_thresh = 0; g.drop_seed = drop_seed; g.drop_seed_dev = drop_seed_dev; g.drop_inv_keep = 1.f; g.drop_ld = ldc;
   g.seg_n = seg_n; g.seg_out = (bf16*)seg_out; g.seg_ld = seg_ld; g.drop_row0 = drop_row0;
   g.r_t = nullptr; g.ld_r = 0; g.r_stats = nullptr; g.r_gamma = nullptr; g.r_beta = nullptr; g.r_rowmask = nullptr;
@@ -540,8 +448,6 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
     g.drop_thresh = fbl_drop_thresh(p_drop);
     g.drop_inv_keep = 1.f / (1.f - p_drop);
   }
-  if (kskip_len && (kskip_steps <= 0 || !accumulate)) return FBL_ERR_ARG;  // only the split-K (accumulating) path skips
-  if (kskip_tilemask && (!kskip_len || M > 32 * 128)) return FBL_ERR_ARG;
   // big tiles only where both dimensions fill them and the grid still covers the chip
   static const int force_small = FBL_ENV_INT("FBL_GEMM_SMALL", 0);
   const bool big = !force_small && !accumulate && (p_drop <= 0.f || seg_n > 0 || tail) && (seg_n <= 0 || (seg_n & 255) == 0) &&
@@ -603,14 +509,13 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
                               out_f32 ? out_f32 + (size_t)m_big * ldc : nullptr,
                               out_bf16 ? (char*)out_bf16 + (size_t)m_big * ldc * 2 : nullptr,
                               out_pre_bf16 ? (char*)out_pre_bf16 + (size_t)m_big * ldc * 2 : nullptr, ldc, 1, 0, 0, 0, 0, 0,
-                              1, nullptr, (rem_mode & 2) ? -3 : -2, a_kblock_stride, nullptr, 0, p_drop, drop_seed, s_rem, seg_n,
+                              1, nullptr, (rem_mode & 2) ? -3 : -2, p_drop, drop_seed, s_rem, seg_n,
                               seg_out ? (char*)seg_out + (size_t)m_big * seg_ld * 2 : nullptr, seg_ld, drop_row0 + m_big, nullptr,
                               nullptr, drop_seed_dev);
         if (rc) return rc;
         if (forked && hipEventRecord(ev_join, (hipStream_t)aux_stream) != hipSuccess) return FBL_ERR_ARG;
         rc = gemm_nt_impl(A, lda, B, ldb, m_big, N, K, bias, rowscale, alpha, act, aux_kind, aux, ld_aux, out_f32,
-                          out_bf16, out_pre_bf16, ldc, 1, 0, 0, 0, 0, 0, 1, nullptr, -1, a_kblock_stride, nullptr, 0,
-                          p_drop, drop_seed, stream, seg_n, seg_out, seg_ld, drop_row0, nullptr, nullptr, drop_seed_dev);
+                          out_bf16, out_pre_bf16, ldc, 1, 0, 0, 0, 0, 0, 1, nullptr, -1, p_drop, drop_seed, stream, seg_n, seg_out, seg_ld, drop_row0, nullptr, nullptr, drop_seed_dev);
         if (rc) return rc;
         if (forked && hipStreamWaitEvent((hipStream_t)stream, ev_join, 0) != hipSuccess) return FBL_ERR_ARG;
         return 0;
@@ -743,7 +648,7 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
   // splitk_reduce_kernel as below -- 463 -> ~235 us.  FBL_GEMM8_SK (measurement builds): 0 = the 128 x 128 two-stage kernel.
   static const int sk8_on = FBL_ENV_INT("FBL_GEMM8_SK", 1);
   bool done = false;
-  if (accumulate && sk8_on && g.ws && batch == 1 && !kskip_len && !a_kblock_stride && M >= 512 && N >= 1024 && (K / BK) % 2 == 0 &&
+  if (accumulate && sk8_on && g.ws && batch == 1 && M >= 512 && N >= 1024 && (K / BK) % 2 == 0 &&
       K / BK >= 128 && (long)M * lda * 2 < (1l << 32) && (long)N * ldb * 2 < (1l << 32)) {
     const int nk = K / BK, tiles = ((M + 255) / 256) * ((N + 255) / 256), n_cu = device_cu_count();
     int want = n_cu / tiles;
@@ -770,18 +675,6 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
     }
   }
   if (done) {
-  } else if (accumulate && kskip_len) {
-    static bool attr_ks = false;
-    auto kfn = gemm_bf16_nt_kernel<4, FBL_ACT_NONE, FBL_AUX_NONE, true, 0, 4, true>;
-    constexpr int smem_bytes = KSKIP_SMEM_BYTES > TileCfg<4>::SMEM_BYTES ? KSKIP_SMEM_BYTES : TileCfg<4>::SMEM_BYTES;
-    if (N > 64 || (K / BK + splitk - 1) / splitk > KSKIP_MAX_STEPS) return FBL_ERR_SHAPE;  // (64 B rows staged, LDS list of valid K-steps)
-    if (K / BK >= 32768) return FBL_ERR_SHAPE;  // the list holds ABSOLUTE k-step indices as int16
-    if (!attr_ks) {
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-      if (e != hipSuccess) return (int)e;
-      attr_ks = true;
-    }
-    hipLaunchKernelGGL(kfn, grid, dim3(256), smem_bytes, (hipStream_t)stream, g);
   } else if (accumulate) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_NONE, true);
   else if (act == FBL_ACT_GELU && aux_kind == FBL_AUX_NONE) FBL_GEMM_LAUNCH(FBL_ACT_GELU, FBL_AUX_NONE, false);
   else if (act == FBL_ACT_RELU && aux_kind == FBL_AUX_NONE) FBL_GEMM_LAUNCH(FBL_ACT_RELU, FBL_AUX_NONE, false);
@@ -822,13 +715,11 @@ extern "C" int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64
                                 const void* aux, int64_t ld_aux, float* out_f32, void* out_bf16, void* out_pre_bf16,
                                 int64_t ldc, int batch, int64_t strideA, int64_t strideB, int64_t strideC,
                                 int64_t strideAux, int64_t strideBias, int splitk, float* splitk_ws,
-                                int64_t splitk_ws_floats, int64_t a_kblock_stride, const int32_t* kskip_len, int kskip_steps,
-                                const uint32_t* kskip_tilemask, void* stream, void* aux_stream) {
+                                int64_t splitk_ws_floats, void* stream, void* aux_stream) {
   if (aux_kind == FBL_AUX_ADAPTER_TAIL) return FBL_ERR_ARG;  // (has its own entry point: fbl_adapter_up_resid_fwd)
   return gemm_nt_impl(A, lda, B, ldb, M, N, K, bias, rowscale, alpha, act, aux_kind, aux, ld_aux, out_f32, out_bf16,
                       out_pre_bf16, ldc, batch, strideA, strideB, strideC, strideAux, strideBias, splitk, splitk_ws,
-                      splitk_ws_floats, a_kblock_stride, kskip_len, kskip_steps, 0.f, 0, stream, 0, nullptr, 0, 0, aux_stream,
-                      nullptr, nullptr, kskip_tilemask);
+                      splitk_ws_floats, 0.f, 0, stream, 0, nullptr, 0, 0, aux_stream);
 }
 
 // z[M, A] = dropout(relu(x[M,K] . Wd[A,K]^T + bd)): the adapter's down-projection with ReLU AND dropout in the GEMM
@@ -837,7 +728,7 @@ extern "C" int fbl_adapter_down_fwd(const void* x_bf16, int64_t ldx, const void*
                                     const float* bias, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* z_bf16,
                                     int64_t ldz, void* stream) {
   return gemm_nt_impl(x_bf16, ldx, wd_bf16, ldw, M, A, K, bias, nullptr, 1.0f, FBL_ACT_RELU, FBL_AUX_NONE, nullptr, 0,
-                      nullptr, z_bf16, nullptr, ldz, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, 0, nullptr, 0, p_drop, seed, stream, 0,
+                      nullptr, z_bf16, nullptr, ldz, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, p_drop, seed, stream, 0,
                       nullptr, 0, 0, nullptr, nullptr, seed_dev);
 }
 
@@ -854,7 +745,7 @@ extern "C" int fbl_dense_adapter_down_fwd(const void* x_bf16, int64_t ldx, const
                                           void* stream, void* aux_stream) {
   if (A <= 0 || (N1 & 63)) return FBL_ERR_ARG;
   return gemm_nt_impl(x_bf16, ldx, wm_bf16, ldw, M, N1 + A, K, bias_m, nullptr, 1.0f, FBL_ACT_NONE, FBL_AUX_NONE, nullptr, 0,
-                      y_f32, y_bf16, nullptr, ldy, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, 0, nullptr, 0, p_drop, seed, stream, N1,
+                      y_f32, y_bf16, nullptr, ldy, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, p_drop, seed, stream, N1,
                       z_bf16, ldz, 0, aux_stream, nullptr, seed_dev);
 }
 
@@ -868,7 +759,7 @@ extern "C" int fbl_adapter_up_resid_fwd(const void* z_bf16, int64_t ldz, const v
   if (ldx % 8) return FBL_ERR_ALIGN;
   const TailArgs tail{r_t, ld_r, r_stats, r_gamma, r_beta, r_rowmask};
   return gemm_nt_impl(z_bf16, ldz, wu_bf16, ldw, M, H, A, bias_u, nullptr, 1.0f, FBL_ACT_NONE, FBL_AUX_ADAPTER_TAIL, x_bf16, ldx,
-                      out_t, nullptr, nullptr, ldt, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, 0, nullptr, 0, p_drop, seed, stream, 0,
+                      out_t, nullptr, nullptr, ldt, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, p_drop, seed, stream, 0,
                       nullptr, 0, 0, nullptr, &tail, seed_dev);
 }
 

@@ -321,7 +321,7 @@ int launch_gemm8_splitk(const GemmArgs& g, hipStream_t stream) {
 bool gemm8_eligible(const GemmArgs& g) {
   const int nk = g.K / BK;
   if (g.K % BK || nk < 4 || (nk & 1)) return false;
-  if (g.a_kblk || g.kskip_len || g.splitk != 1 || (g.drop_thresh && g.seg_n <= 0)) return false;
+  if (g.splitk != 1 || (g.drop_thresh && g.seg_n <= 0)) return false;
   if ((long)g.M * g.lda * 2 >= (1l << 32) || (long)g.N * g.ldb * 2 >= (1l << 32)) return false;
   return true;
 }

@@ -88,8 +88,7 @@ class Engine:
         L.load()
         self.dev = dev
         self.opts = dict(getattr(model, "engine_options", None) or {})
-        unknown = set(self.opts) - {"eager_logits", "side_stream", "fold_dx", "dw_on_side", "fuse_tail", "merge", "dw_group", "attn_save_p",
-                                    "pos_grad_gt", "attn_fused_dk", "attn_toeplitz_dq"}
+        unknown = set(self.opts) - {"eager_logits", "side_stream", "fold_dx", "dw_on_side", "fuse_tail", "merge", "dw_group", "attn_save_p"}
         if unknown:
             raise ValueError(f"unknown engine_options: {sorted(unknown)}")
         self._build_flat()
@@ -131,15 +130,10 @@ class Engine:
         self.use_side_stream = bool(o.get("side_stream", True))
         self.fold_dx = bool(o.get("fold_dx", True))
         self.dw_on_side = bool(o.get("dw_on_side", False))
-        #   attn_save_p    False = the attention backward recomputes the probabilities (rounds 1-5) instead of reading the ones the
-        #                  training forward saved (157 MB per layer execution at the bench shape, held until the backward)
+        #   attn_save_p    False = the attention backward recomputes the probabilities and forms dK by the key-major shear pass
+        #                  instead of reading the ones the training forward saved (157 MB per layer execution at the bench shape,
+        #                  held until the backward)
         self.attn_save_p = bool(o.get("attn_save_p", True))
-        #   pos_grad_gt    True = position-table gradients through G^T and split-K GEMMs (rounds 1-5) instead of fbl_attn_pos_grad
-        self.pos_grad_gt = bool(o.get("pos_grad_gt", False))
-        #   attn_fused_dk  False = dK by the separate key-major shear pass (rounds 1-5) instead of inside kernel A (fbl_disent_attn_bwd_dspk)
-        self.attn_fused_dk = bool(o.get("attn_fused_dk", True))
-        #   attn_toeplitz_dq  False = dQ by the scatter-based query-major shear pass (rounds 1-5) instead of fbl_disent_attn_bwd_dq
-        self.attn_toeplitz_dq = bool(o.get("attn_toeplitz_dq", True))
         self.fuse_tail = bool(o.get("fuse_tail", True))
         L.exclude_from_aux(self.side)  # side-stream GEMMs never fork into the aux stream of the main stream's GEMMs
         self.dw_group = max(1, min(L.ADW_MAX_ADAPTERS, int(o.get("dw_group", 16))))  # adapter gradient products per launch (<= 16)
@@ -1166,20 +1160,14 @@ class Engine:
         if self.reducer is not None:  # ~0.15 ms (0.35 until round 6) without one-workgroup-per-CU GEMM tiles: where gradient collectives may start
             self.reducer.window()
 
-        # The position-table products of this execution (dPK = G1^T.Q, dPQ = G2^T.K) are NOT formed here: the shear passes and
-        # the preparation kernel write their operands into this execution's slice of per-step tensors, and one strided-batch
-        # chain at the END of backward handles all executions (attn_bwd.pos_table_grads_batched).  ft_ln=False: nothing
-        # trainable sits behind the position tables, the operands are scratch.
+        # The position-table gradients of this execution (dPK = G1^T.Q, dPQ = G2^T.K) are NOT formed here: its dS / dS^T and
+        # q / k go on the per-step lists, and one chain at the END of backward handles all executions
+        # (attn_bwd.pos_table_grads_batched).  ft_ln=False: nothing trainable sits behind the position tables, nothing is kept.
         pc = getattr(run, "pos_chain", None)
-        bufs = None
+        st = disent_attn_bwd(self, run, sv, dctx, dqkv, None, defer_pos=True)
         if pc is not None:
-            e = pc["n"]
-            if "G1T" in pc:
-                bufs = (pc["G1T"][e], pc["G2T"][e], pc["QT"][e], pc["KT"][e])
             pc["seeds"].append(sv.seed_pos)
-            pc["n"] = e + 1
-        st = disent_attn_bwd(self, run, sv, dctx, dqkv, None, defer_pos=True, bufs=bufs)
-        if pc is not None and "X1" in pc:  # the fused position-gradient kernel reads these at the end of backward
+            pc["n"] += 1
             pc["X1"].append(st["dS"]); pc["X2"].append(st["dST"]); pc["Yq"].append(st["q"]); pc["Yk"].append(st["k"])
             pc["klen"], pc["row0"] = st["klen"], st["row0"]
         return dqkv

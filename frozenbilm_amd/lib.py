@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("FBL_LIB") or os.path.join(HERE, "libfbl.so")
 
 ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_GRAD = 0, 1, 2, 3
 AUX_NONE, AUX_ADD_F32, AUX_ADD_BF16, AUX_MUL_DGELU_BF16, AUX_MUL_POS_BF16, AUX_MUL_BF16 = 0, 1, 2, 3, 4, 5
-ABI_VERSION = 8  # fbl_abi_version() of the library this binding was written against (argument lists change with it)
+ABI_VERSION = 9  # fbl_abi_version() of the library this binding was written against (argument lists change with it)
 
 _vp, _i, _l, _f, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
@@ -25,7 +25,7 @@ _vp, _i, _l, _f, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 SIGNATURES = {
     "fbl_abi_version": (_i, []),
     "fbl_gemm_bf16_nt": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _l,
-                              _l, _l, _l, _i, _vp, _l, _l, _vp, _i, _vp, _vp, _vp]),
+                              _l, _l, _l, _i, _vp, _l, _vp, _vp]),
     "fbl_adapter_down_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _f, _u64, _vp, _vp, _l, _vp]),
     "fbl_dense_adapter_down_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp, _vp, _l, _f, _u64, _vp, _vp, _l, _vp, _vp]),
     "fbl_adapter_up_resid_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _l, _f, _u64, _vp, _vp, _l, _vp, _vp, _vp, _vp,
@@ -54,18 +54,14 @@ SIGNATURES = {
                                  _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "fbl_disent_attn_probs": (_i, [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
     "fbl_attn_rowdot": (_i, [_vp, _vp, _l, _vp, _i, _i, _i, _vp]),
-    "fbl_attn_bwd_prep": (_i, [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "fbl_attn_bwd_prep": (_i, [_vp, _l, _vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "fbl_disent_attn_bwd_dq": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _vp]),
     "fbl_disent_attn_bwd_dspk": (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l,
                                       _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "fbl_disent_attn_bwd_ds": (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _f, _f, _u64, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_disent_attn_bwd_dsp": (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _vp,
-                                     _i, _i, _i, _i, _vp, _vp]),
-    "fbl_disent_attn_bwd_shear": (_i, [_i, _vp, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _i,
-                                       _vp, _vp, _vp]),
+    "fbl_disent_attn_bwd_shear": (_i, [_vp, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "fbl_attn_pos_grad": (_i, [_i, _vp, _vp, _l, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "fbl_gt_tilemask": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "fbl_ce_fwd": (_i, [_vp, _l, _vp, _i, _i, _vp, _vp, _vp]),
     "fbl_ce_bwd_rows": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "fbl_gather_rows_bf16": (_i, [_vp, _l, _vp, _i, _i, _vp, _vp]),
@@ -202,8 +198,7 @@ def gemm_plan(M, N, K, batch=1, splitk=1):
 
 
 def gemm(A, B, *, bias=None, rowscale=None, alpha=1.0, act=ACT_NONE, aux=None, aux_kind=AUX_NONE, out_f32=None,
-         out_bf16=None, out_pre=None, splitk=1, M=None, N=None, ws=None, K=None, a_kblock=0, kskip_len=None, kskip_steps=0,
-         kskip_tilemask=None):
+         out_bf16=None, out_pre=None, splitk=1, M=None, N=None, ws=None):
     """out[M,N] = epi(alpha * A[M,K] @ B[N,K]^T).  A/B: bf16 2-D views (or 3-D for strided batch)."""
     _req(A, torch.bfloat16, "A")
     _req(B, torch.bfloat16, "B")
@@ -216,11 +211,9 @@ def gemm(A, B, *, bias=None, rowscale=None, alpha=1.0, act=ACT_NONE, aux=None, a
     else:
         A2, B2 = A, B
     lda, ldb = _rows2d(A2, "A"), _rows2d(B2, "B")
-    Mv, Kv = A2.shape
+    Mv, K = A2.shape
     Nv = B2.shape[0]
-    if K is None:
-        K = Kv
-        assert B2.shape[1] == K, (A2.shape, B2.shape)
+    assert B2.shape[1] == K, (A2.shape, B2.shape)
     M = Mv if M is None else M
     N = Nv if N is None else N
     ldc = None
@@ -250,8 +243,7 @@ def gemm(A, B, *, bias=None, rowscale=None, alpha=1.0, act=ACT_NONE, aux=None, a
         _req(rowscale, torch.float32, "rowscale")
     code = load().fbl_gemm_bf16_nt(_p(A), lda, _p(B), ldb, M, N, K, _p(bias), _p(rowscale), float(alpha), act, aux_kind,
                                    _p(aux), ld_aux, _p(out_f32), _p(out_bf16), _p(out_pre), ldc or 0, batch, sA, sB, sC,
-                                   sX, sBias, splitk, _p(ws), (ws.numel() if ws is not None else 0), int(a_kblock),
-                                   _p(kskip_len), int(kskip_steps), _p(kskip_tilemask), _stream(), _aux_stream())
+                                   sX, sBias, splitk, _p(ws), (ws.numel() if ws is not None else 0), _stream(), _aux_stream())
     _chk(code, "fbl_gemm_bf16_nt")
 
 
@@ -516,7 +508,7 @@ def _row0(row0, B, klen):
 def disent_attn_fwd(q, k, v, pk, pq, relidx, mask, scale, ctx, lse, B, S, Sp, nh, span2, p_drop=0.0, seed=0, klen=None,
                     border=None, lin=0, row0=None, psave=None, msave=None):
     """psave bf16 [B,nh,Sp,Sp] + msave fp32 [B,nh,Sp/64,S] (training): the forward leaves its un-normalised probabilities
-    for fbl_disent_attn_bwd_dsp (include/fbl.h)"""
+    for fbl_disent_attn_bwd_dspk (include/fbl.h)"""
     if psave is not None:
         _req(psave, torch.bfloat16, "psave"); _req(msave, torch.float32, "msave")
         assert psave.is_contiguous() and msave.is_contiguous()
@@ -544,12 +536,12 @@ def disent_attn_probs(q, k, pk, pq, relidx, mask, lse, scale, probs, B, S, nh):
                                       _p(probs), B, S, nh, _stream()), "fbl_disent_attn_probs")
 
 
-def attn_bwd_prep(q, k, pq, pk, dO, O, QT, KT, PQT, PKT, Dv, B, S, Sp, nh, span2, row0=None, relidx=None, PQX=None, PKX=None):
-    """K^T, Q^T (head-major), PK^T, PQ^T, D = rowdot(dO, O) and the index-expanded tables PQX / PKX [nh,2*Sp,64] in one launch
-    (see fbl.h); every output but Dv may be None"""
+def attn_bwd_prep(q, pq, pk, dO, O, QT, PQT, Dv, B, S, Sp, nh, span2, row0=None, relidx=None, PQX=None, PKX=None):
+    """D = rowdot(dO, O), the index-expanded tables PQX / PKX [nh,2*Sp,64] and Q^T (head-major), PQ^T in one launch (see
+    fbl.h); every output but Dv may be None"""
     ldq, ldp, ldo = _rows2d(q, "q"), _rows2d(pq, "pq"), _rows2d(dO, "dO")
-    assert _rows2d(k, "k") == ldq and _rows2d(pk, "pk") == ldp and _rows2d(O, "O") == ldo
-    for t in (QT, KT, PQT, PKT, PQX, PKX):
+    assert _rows2d(pk, "pk") == ldp and _rows2d(O, "O") == ldo
+    for t in (QT, PQT, PQX, PKX):
         if t is not None:
             _req(t, torch.bfloat16, "transposed output")
             assert t.is_contiguous()
@@ -557,8 +549,8 @@ def attn_bwd_prep(q, k, pq, pk, dO, O, QT, KT, PQT, PKT, Dv, B, S, Sp, nh, span2
         if t is not None:
             _req(relidx, torch.int16, "relidx")
             assert t.numel() == nh * 64 * 2 * Sp and relidx.numel() == 2 * S - 1
-    _chk(load().fbl_attn_bwd_prep(_p(q), _p(k), ldq, _p(pq), _p(pk), ldp, _p(dO), _p(O), ldo, _p(QT), _p(KT), _p(PQT), _p(PKT),
-                                  _p(Dv), _p(relidx), _p(PQX), _p(PKX), B, S, Sp, nh, span2, _row0(row0, B, True), _stream()),
+    _chk(load().fbl_attn_bwd_prep(_p(q), ldq, _p(pq), _p(pk), ldp, _p(dO), _p(O), ldo, _p(QT), _p(PQT), _p(Dv), _p(relidx),
+                                  _p(PQX), _p(PKX), B, S, Sp, nh, span2, _row0(row0, B, True), _stream()),
          "fbl_attn_bwd_prep")
 
 
@@ -578,18 +570,6 @@ def disent_attn_bwd_ds(q, k, v, dO, pk, pq, relidx, mask, lse, Dv, scale, dV, dS
                                        _p(relidx), _p(mask), _p(klen), _p(border), _p(lse), _p(Dv), float(scale), float(p_drop), int(seed), _seed_dev(),
                                        _p(dV), lddv, _p(dS), _p(dST), B, S, Sp, nh, span2, int(lin), _row0(row0, B, klen), _stream()),
          "fbl_disent_attn_bwd_ds")
-
-
-def disent_attn_bwd_dsp(psave, msave, v, dO, lse, Dv, scale, dV, dS, dST, B, S, Sp, nh, p_drop=0.0, seed=0, klen=None,
-                        border=None, row0=None):
-    """kernel A of the attention backward from the probabilities the training forward saved (no recomputation of the scores)"""
-    _req(psave, torch.bfloat16, "psave"); _req(msave, torch.float32, "msave")
-    assert psave.is_contiguous() and msave.is_contiguous()
-    assert psave.numel() == B * nh * Sp * Sp and msave.numel() == B * nh * (Sp // 64) * S
-    ldv, ldo, lddv = _rows2d(v, "v"), _rows2d(dO, "dO"), _rows2d(dV, "dV")
-    _chk(load().fbl_disent_attn_bwd_dsp(_p(psave), _p(msave), _p(v), ldv, _p(dO), ldo, _p(klen), _p(border), _p(lse), _p(Dv),
-                                        float(scale), float(p_drop), int(seed), _seed_dev(), _p(dV), lddv, _p(dS), _p(dST),
-                                        B, S, Sp, nh, _row0(row0, B, klen), _stream()), "fbl_disent_attn_bwd_dsp")
 
 
 def disent_attn_bwd_dspk(psave, msave, q, v, dO, pqx, lse, Dv, scale, dK, dV, dS, dST, B, S, Sp, nh, p_drop=0.0, seed=0, klen=None,
@@ -631,21 +611,13 @@ def attn_pos_grad(neg, Xs, Ys, dlo, dcnt, dcnt_max, out, B, S, Sp, nh, rcnt, kle
                                   E, B, S, Sp, nh, int(rcnt), _stream()), "fbl_attn_pos_grad")
 
 
-def gt_tilemask(relidx, klen, B, S, Sp, span2, neg, rmin, rcnt):
-    """uint32 [B * Sp/64] (as int32 tensor): the 128-row tiles of G^T each 64-row k-step can touch (include/fbl.h)"""
-    mask = torch.empty(B * (Sp // 64), dtype=torch.int32, device=relidx.device)
-    _chk(load().fbl_gt_tilemask(_p(relidx), _p(klen), B, S, Sp, span2, int(neg), int(rmin), int(rcnt), _p(mask), _stream()),
-         "fbl_gt_tilemask")
-    return mask
-
-
-def disent_attn_bwd_shear(neg, X, YT, PT, relidx, out, GT, B, S, Sp, nh, span2, y_head_major=True, klen=None,
-                          rmin=0, rcnt=None, lin=0, border=None, row0=None, tilemask=None):
-    ldout = _rows2d(out, "out")
-    sh, sb, sd = head_strides(B, Sp, nh, y_head_major)
-    _chk(load().fbl_disent_attn_bwd_shear(int(neg), _p(X), _p(YT), sh, sb, sd, _p(PT), _p(relidx), _p(klen), _p(border), _p(out), ldout,
-                                          _p(GT), rmin, span2 if rcnt is None else rcnt, int(lin), B, S, Sp, nh, span2,
-                                          _row0(row0, B, klen), _p(tilemask), _stream()),
+def disent_attn_bwd_shear(dST, QT, PQT, relidx, dK, B, S, Sp, nh, span2, klen=None, lin=0, border=None, row0=None):
+    """dK = dS^T.Q + G2.PQ by the key-major shear pass of the recompute route (include/fbl.h fbl_disent_attn_bwd_shear);
+    QT / PQT: the head-major Q^T and PQ^T of attn_bwd_prep"""
+    lddk = _rows2d(dK, "dK")
+    sh, sb, sd = head_strides(B, Sp, nh, True)
+    _chk(load().fbl_disent_attn_bwd_shear(_p(dST), _p(QT), sh, sb, sd, _p(PQT), _p(relidx), _p(klen), _p(border), _p(dK), lddk,
+                                          int(lin), B, S, Sp, nh, span2, _row0(row0, B, klen), _stream()),
          "fbl_disent_attn_bwd_shear")
 
 

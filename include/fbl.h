@@ -48,7 +48,10 @@ enum {
   FBL_AUX_ADAPTER_TAIL = 6    /* internal to fbl_adapter_up_resid_fwd; fbl_gemm_bf16_nt rejects it                */
 };
 
-/* Bumped whenever the exported interface changes (6: this header -- fbl_dropout_sum_f32, fbl_zero, fbl_heads_to_rows_bf16, fbl_gt_tilemask added; tile masks on the shear pass and the k-skipping GEMM); the ctypes binding refuses any other value. */
+/* Bumped whenever the exported interface changes (9: the entry points of the superseded attention-backward routes are gone --
+ * kernel A from saved probabilities without dK, the G^T tile masks; fbl_gemm_bf16_nt has no k-blocked / k-skipping operands;
+ * fbl_disent_attn_bwd_shear is the key-major pass only, without G^T; fbl_attn_bwd_prep without K^T / PK^T); the ctypes binding
+ * refuses any other value. */
 int fbl_abi_version(void);
 
 /* C[M,N] = epi(alpha * A[M,K] . B[N,K]^T): bf16 MFMA, fp32 accumulate.  K % 64 == 0, lda/ldb % 8 == 0.
@@ -56,14 +59,6 @@ int fbl_abi_version(void);
  * batch > 1: strided batch (strides in elements).  splitk > 1: ACCUMULATE mode, out_f32 += A.B^T with the K range
  * split over `splitk` workgroup sets; partial tiles go to `splitk_ws` (>= batch*splitk*M*roundup(N,4) floats) and are
  * folded deterministically by a second tiny kernel; with splitk_ws == NULL (or too small) they are atomicAdd-ed.
- * kskip_len != NULL (split-K / accumulate mode only): K consists of samples of kskip_steps 64-wide k-steps each and step j of
- * sample b is known to be all zero in A when 64*j >= kskip_len[b] (int32, device): such steps are neither read nor
- * multiplied -- the rows of G^T beyond a sample's last valid position (fbl_disent_attn_bwd_shear leaves them unwritten).
- * kskip_tilemask != NULL (with kskip_len; uint32 per 64-wide k-step, device): bit t set <=> rows [128t, 128t+128) of A can be
- * non-zero in that k-step; (tile, step) pairs whose bit is clear are neither read nor multiplied (fbl_gt_tilemask: the rows of
- * G^T outside the window a 64-row step can reach, which fbl_disent_attn_bwd_shear then does not even zero-fill).
- * a_kblock_stride > 0: A is k-blocked, A[m][k] lives at m*lda + (k/32)*a_kblock_stride + k%32 (the G^T layout written
- * by fbl_disent_attn_bwd_shear, lda = 32); 0 = plain K-contiguous rows.
  * aux_stream (may be NULL): a second stream of the caller on the same device.  A multi-round problem runs its last,
  * partly filled round as small tiles; with an aux stream those are launched there first, concurrently with the big tiles
  * (fork / join by events inside this call).  NULL: they simply precede the big tiles on `stream`.
@@ -73,10 +68,9 @@ int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, int
                      const float* rowscale, float alpha, int act, int aux_kind, const void* aux, int64_t ld_aux,
                      float* out_f32, void* out_bf16, void* out_pre_bf16, int64_t ldc, int batch, int64_t strideA,
                      int64_t strideB, int64_t strideC, int64_t strideAux, int64_t strideBias, int splitk,
-                     float* splitk_ws, int64_t splitk_ws_floats, int64_t a_kblock_stride, const int32_t* kskip_len,
-                     int kskip_steps, const uint32_t* kskip_tilemask, void* stream, void* aux_stream);
+                     float* splitk_ws, int64_t splitk_ws_floats, void* stream, void* aux_stream);
 
-/* Host-side query, no launch: the kernel fbl_gemm_bf16_nt uses for a plain (K-contiguous, no k-skip) problem of this
+/* Host-side query, no launch: the kernel fbl_gemm_bf16_nt uses for a plain problem of this
  * shape: 8 = the 8-phase 256x256 / 224x256 kernel (gemm8_kernel; remainder rows of a multi-round problem run as 64x128
  * tiles), 2 = the 2-stage 128x128 / 64x128 kernel.  bench.py attributes launches to the dominant kernel with it. */
 int fbl_gemm_plan(int M, int N, int K, int batch, int splitk);
@@ -225,9 +219,8 @@ int fbl_colsum(const void* in, int in_is_bf16, int64_t ld_in, int rows, int cols
                void* stream);
 
 /* Per-head transpose: vt[h*out_sh + b*out_sb + d*out_sd + s] = V[b*S+s, h*64+d] (s < S), 0 for S <= s < Sp.
- * V has row stride ldv (e.g. 3H inside the fused QKV buffer).  Gives the P.V / dS.K / dS^T.Q MFMAs their
- * position-contiguous operands; with (sh, sd, sb) = (64*B*Sp, B*Sp, Sp) the rows are also the K-contiguous operands of
- * the per-head position-table gradient GEMMs. */
+ * V has row stride ldv (e.g. 3H inside the fused QKV buffer).  Gives MFMAs over positions their position-contiguous
+ * operands (the Q^T of the key-major shear pass is this layout with (sh, sb, sd) = (64*B*Sp, Sp, B*Sp)). */
 int fbl_head_transpose(const void* v_bf16, int64_t ldv, void* vt_bf16, int B, int S, int Sp, int nh, int64_t out_sh,
                        int64_t out_sb, int64_t out_sd, void* stream);
 
@@ -248,13 +241,14 @@ int fbl_head_transpose(const void* v_bf16, int64_t ldv, void* vt_bf16, int B, in
  *   (>= klen[b]: every position up to the last valid one has a row; rows a sample does not have are neither read nor
  *   written).  mask, lse and the scratch tensors of the backward keep their padded [B, S(p)] indexing.  The rows that
  *   exist receive exactly the values of the padded layout.  The same argument on the three backward entry points below
- *   (fbl_attn_bwd_prep: q / k / dO / O; fbl_disent_attn_bwd_ds: q / k / v / dO / dV; fbl_disent_attn_bwd_shear: out).
+ *   (fbl_attn_bwd_prep: q / dO / O; fbl_disent_attn_bwd_ds: q / k / v / dO / dV; fbl_disent_attn_bwd_shear: dK;
+ *   fbl_disent_attn_bwd_dspk and fbl_disent_attn_bwd_dq take it too).
  *   psave / msave (optional, both or neither; training): the forward also leaves what the backward would otherwise
  *   recompute -- psave bf16 [B,nh,Sp,Sp]: psave[b,h,i,j] = exp2(k2*(s_ij - m)) with s the unscaled score, k2 = scale*log2(e)
  *   and m the running row maximum when key tile j/64 was processed (BEFORE dropout, exactly 0 for masked keys; the SIGN BIT
  *   carries the dropout decision of the pair: set = dropped, so the backward does not regenerate the mask); msave fp32
  *   [B,nh,Sp/64,S]: msave[b,h,j/64,i] = k2*m.  P_ij = psave_ij * exp2(msave - lse_i*log2(e)).  Only the tile pairs the forward
- *   visits (both tile indices below ceil(klen/64)) are written -- fbl_disent_attn_bwd_dsp reads exactly those.
+ *   visits (both tile indices below ceil(klen/64)) are written -- fbl_disent_attn_bwd_dspk reads exactly those.
  * ref: model/deberta.py:717-818 (forward), :820-947 (disentangled_attention_bias), :100-138 (XSoftmax). */
 int fbl_disent_attn_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
                         const void* pk, const void* pq, int64_t ldp, const int16_t* relidx,
@@ -270,81 +264,66 @@ int fbl_disent_attn_probs(const void* q, const void* k, int64_t ldq, const void*
                           const int16_t* relidx, const int32_t* mask, const float* lse, float scale, float* probs, int B,
                           int S, int nh, void* stream);
 
-/* Backward of fbl_disent_attn_fwd, three launches (ref: autograd of model/deberta.py:717-947, XSoftmax.backward
- * :134-138, XDropout.backward :185-190):
- *  fbl_attn_rowdot:            Dv[b,h,i] = dO_i . O_i  (per head).
+/* Backward of fbl_disent_attn_fwd (ref: autograd of model/deberta.py:717-947, XSoftmax.backward :134-138, XDropout.backward
+ * :185-190).  Two routes:
+ *   training forward saved P:  fbl_attn_bwd_prep (Dv, PQX, PKX) -> fbl_disent_attn_bwd_dspk (dV, dK, dS, dS^T)
+ *                              -> fbl_disent_attn_bwd_dq (dQ) -> fbl_attn_pos_grad (dPK, dPQ; all layer executions at once)
+ *   no saved P (recompute):    fbl_attn_bwd_prep (Dv, PKX, QT, PQT) -> fbl_disent_attn_bwd_ds (dV, dS, dS^T)
+ *                              -> fbl_disent_attn_bwd_dq (dQ) -> fbl_disent_attn_bwd_shear (dK) -> fbl_attn_pos_grad
+ *  fbl_attn_rowdot:            Dv[b,h,i] = dO_i . O_i  (per head; fbl_attn_bwd_prep computes it too).
  *  fbl_disent_attn_bwd_ds:     recomputes P; writes dV (bf16, into a row-major buffer), dS and dS^T (bf16 [B,nh,Sp,Sp],
  *                              dS = P*(dP - Dv)*scale, exactly 0 where masked / padded; with klen only the
  *                              [klen x klen] corner (rounded up to 64) is written and read).
- *  fbl_disent_attn_bwd_shear:  neg=0: out = dQ = dS.K + G1.PK,  G1[i,r] = sum_{j: idx(i-j)=r} dS[i,j]
- *                              neg=1: out = dK = dS^T.Q + G2.PQ, G2[j,r] = sum_{i: idx(i-j)=r} dS[i,j]
- *                              X = dS / dS^T; YT = transposed K / Q (fbl_head_transpose strides); PT = transposed
- *                              PK / PQ [nh][64][span2]; also writes GT = G^T (bf16), the A operand of the position-table
- *                              gradient GEMM dPK[h] = G1T[h] . QT[h]^T (dPQ: G2T, KT), k-blocked so that every
- *                              workgroup writes one contiguous block: GT[h][b][t][r][32] with t = row/32, r in
- *                              [0, gt_rcnt) standing for table row gt_rmin + r (the range of relidx; others are 0).
+ *  fbl_disent_attn_bwd_shear:  the key-major pass: dK = dS^T.Q + G2.PQ, G2[j,r] = sum_{i: idx(i-j)=r} dS[i,j]
+ *                              dST = dS^T; QT = transposed Q (fbl_head_transpose strides y_sh / y_sb / y_sd); PQT = transposed
+ *                              PQ [nh][64][span2]; dK bf16 rows (row stride lddk, head h at column h*64).
  *                              lin_span: |i-j| < lin_span => relidx is injective there (identity buckets, = position_buckets/2;
- *                              0 if unknown): those entries are scattered with plain LDS stores instead of atomics.
- * With klen given, G^T blocks (32 rows) of 64-row steps that start beyond klen[b] are left UNWRITTEN: their consumer
- * (fbl_gemm_bf16_nt with kskip_len = klen) never reads them. */
+ *                              0 if unknown): those entries are scattered with plain LDS stores instead of atomics. */
 int fbl_attn_rowdot(const void* dO, const void* O, int64_t ld, float* out, int B, int S, int nh, void* stream);
-/* Position-table gradients of E layer executions in one launch, straight from the dS / dS^T tensors of fbl_disent_attn_bwd_ds(p):
+/* Position-table gradients of E layer executions in one launch, straight from the dS / dS^T tensors of fbl_disent_attn_bwd_ds(pk):
  *   neg = 0: out[e][h][r][d] = dPK = sum_b sum_{(i,j): relidx(i-j) = rmin + r} dS[i,j] * Q[b*S+i, h*64+d]     (X = dS,   Y = q)
  *   neg = 1: out[e][h][r][d] = dPQ = sum_b sum_{(i,j): relidx(i-j) = rmin + r} dS[i,j] * K[b*S+j, h*64+d]     (X = dS^T, Y = k)
  * X, Y: HOST arrays of E device pointers (X[e]: bf16 [B,nh,Sp,Sp]; Y[e]: bf16 rows of stride ldy, packed by row0 if given);
  * dlo / dcnt int16 [rcnt] (device): table row rmin + r collects the deltas i-j in [dlo[r], dlo[r] + dcnt[r]) (relidx is
- * monotone: the inverse of the index vector), dcnt_max = max(dcnt) (host value); klen as in fbl_disent_attn_bwd_ds (only the written corner of X is read);
- * out fp32 [E, nh, rcnt, 64], fully written (no accumulation, no workspace, bit-reproducible).  When this entry point is used
- * fbl_disent_attn_bwd_shear may be called with GT = NULL (no G^T is written).
+ * monotone: the inverse of the index vector), dcnt_max = max(dcnt) (host value, 1..8: FBL_ERR_ARG beyond); klen as in
+ * fbl_disent_attn_bwd_ds (only the written corner of X is read);
+ * out fp32 [E, nh, rcnt, 64], fully written (no accumulation, no workspace, bit-reproducible).
  * ref: autograd of model/deberta.py:870-918 (c2p / p2c gathers) and :847-853 (the position projections' inputs). */
 int fbl_attn_pos_grad(int neg, const void* const* X, const void* const* Y, int64_t ldy, const int16_t* dlo, const int16_t* dcnt,
                       int dcnt_max, const int32_t* klen, const int32_t* row0, float* out, int E, int B, int S, int Sp, int nh,
                       int rcnt, void* stream);
-/* mask[b*(Sp/64) + j] (uint32): which 128-row tiles of the gt_rcnt rows of G^T (row 0 = table row gt_rmin) the 64-row k-step j of
- * sample b can touch (neg as in fbl_disent_attn_bwd_shear; klen optional).  A function of the lengths and the relative-index map only:
- * computed once per backward pass and handed to every shear launch (gt_tilemask: rows outside the marked tiles are not written)
- * and to the position-table products (fbl_gemm_bf16_nt kskip_tilemask: not read).  ref: the index arithmetic of
- * model/deberta.py:870-918 (c2p / p2c gather ranges). */
-int fbl_gt_tilemask(const int16_t* relidx, const int32_t* klen, int B, int S, int Sp, int span2, int neg, int gt_rmin, int gt_rcnt,
-                    uint32_t* mask, void* stream);
-/* The preparation of one attention backward as ONE launch: QT / KT = fbl_head_transpose of q / k (head-major
- * [nh,64,B,Sp]), PQT / PKT = the same of the position projections ([nh,64,span2]), Dv = fbl_attn_rowdot(dO, O), and the
- * position tables EXPANDED by the relative-index map for the fused key-major pass (fbl_disent_attn_bwd_dspk):
+/* The preparation of one attention backward as ONE launch: Dv = fbl_attn_rowdot(dO, O), the position tables EXPANDED by the
+ * relative-index map for the Toeplitz passes (fbl_disent_attn_bwd_dspk, fbl_disent_attn_bwd_dq):
  *   PQX[h][t][d] = pq[relidx[clamp(t - Sp + S - 1, 0, 2S-2)]][h*64 + d],  t in [0, 2 Sp)  (t - Sp = delta = i - j),
- * bf16 [nh,2*Sp,64]; PKX the same of pk.  Every output but Dv is optional (NULL: not produced); PQX / PKX need relidx.
+ * bf16 [nh,2*Sp,64]; PKX the same of pk; and for the key-major shear pass QT = fbl_head_transpose of q (head-major
+ * [nh,64,B,Sp]) and PQT = the same of pq ([nh,64,span2]).  Every output but Dv is optional (NULL: not produced); PQX / PKX
+ * need relidx.
  * ref: transpose_for_scores model/deberta.py:712-715 (position-contiguous operand copies), XSoftmax.backward :134-138 (D),
  * the c2p / p2c gathers :870-918 (the index map the expansion applies once per table instead of once per score). */
-int fbl_attn_bwd_prep(const void* q, const void* k, int64_t ldq, const void* pq, const void* pk, int64_t ldp, const void* dO,
-                      const void* O, int64_t ldo, void* QT, void* KT, void* PQT, void* PKT, float* Dv, const int16_t* relidx,
-                      void* PQX, void* PKX, int B, int S, int Sp, int nh, int span2, const int32_t* row0, void* stream);
+int fbl_attn_bwd_prep(const void* q, int64_t ldq, const void* pq, const void* pk, int64_t ldp, const void* dO, const void* O,
+                      int64_t ldo, void* QT, void* PQT, float* Dv, const int16_t* relidx, void* PQX, void* PKX, int B, int S,
+                      int Sp, int nh, int span2, const int32_t* row0, void* stream);
 int fbl_disent_attn_bwd_ds(const void* q, const void* k, const void* v, int64_t ldq, const void* dO, int64_t ldo,
                            const void* pk, const void* pq, int64_t ldp, const int16_t* relidx, const int32_t* mask, const int32_t* klen,
                            const int32_t* border, const float* lse, const float* Dv,
                            float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* dV, int64_t lddv, void* dS, void* dST, int B,
                            int S, int Sp, int nh, int span2, int lin_span, const int32_t* row0, void* stream);
-/* fbl_disent_attn_bwd_ds without the recomputation: P and the dropout mask come from the psave / msave a training forward left
- * (see fbl_disent_attn_fwd; p_drop gives the scale of the kept pairs, the seed arguments are not read); same outputs (dV, dS,
- * dS^T), q / k / position tables not needed.
- * ref: autograd of model/deberta.py:789-818 (softmax, dropout, context), XSoftmax.backward :134-138, XDropout.backward :185-190. */
-int fbl_disent_attn_bwd_dsp(const void* psave, const float* msave, const void* v, int64_t ldv, const void* dO, int64_t ldo,
-                            const int32_t* klen, const int32_t* border, const float* lse, const float* Dv, float scale,
-                            float p_drop, uint64_t seed, const uint64_t* seed_dev, void* dV, int64_t lddv, void* dS, void* dST,
-                            int B, int S, int Sp, int nh, const int32_t* row0, void* stream);
-int fbl_disent_attn_bwd_shear(int neg, const void* X, const void* YT, int64_t y_sh, int64_t y_sb, int64_t y_sd,
-                              const void* PT, const int16_t* relidx, const int32_t* klen, const int32_t* border,
-                              void* out, int64_t ldout,
-                              void* GT, int gt_rmin, int gt_rcnt, int lin_span, int B, int S, int Sp, int nh,
-                              int span2, const int32_t* row0, const uint32_t* gt_tilemask, void* stream);
-/* The query-major half in Toeplitz form: dQ = dS.K + G1.PK (what fbl_disent_attn_bwd_shear(neg = 0) computes) from the dS of
- * fbl_disent_attn_bwd_ds / _dsp / _dspk, k bf16 rows, and pkx = the PKX of fbl_attn_bwd_prep -- no index table, no scatter, no
+int fbl_disent_attn_bwd_shear(const void* dST, const void* QT, int64_t y_sh, int64_t y_sb, int64_t y_sd, const void* PQT,
+                              const int16_t* relidx, const int32_t* klen, const int32_t* border, void* dK, int64_t lddk,
+                              int lin_span, int B, int S, int Sp, int nh, int span2, const int32_t* row0, void* stream);
+/* The query-major half in Toeplitz form: dQ = dS.K + G1.PK,  G1[i,r] = sum_{j: idx(i-j)=r} dS[i,j],  from the dS of
+ * fbl_disent_attn_bwd_ds / _dspk, k bf16 rows, and pkx = the PKX of fbl_attn_bwd_prep -- no index table, no scatter, no
  * transposed copies of K / PK.  klen / border / row0 (packed rows of k and dQ) as above.
  * ref: autograd of model/deberta.py:756-765 (QK^T) and of the c2p term :870-894. */
 int fbl_disent_attn_bwd_dq(const void* dS, const void* k, int64_t ldk, const void* pkx, const int32_t* klen, const int32_t* border,
                            void* dQ, int64_t lddq, int B, int S, int Sp, int nh, const int32_t* row0, void* stream);
-/* fbl_disent_attn_bwd_dsp + the key-major shear pass in one kernel: besides dV, dS and dS^T it forms
- *   dK = dS^T.Q + G2.PQ  (what fbl_disent_attn_bwd_shear(neg = 1) computes from dS^T) -- the second term as a Toeplitz product
+/* fbl_disent_attn_bwd_ds without the recomputation, plus the key-major pass: P and the dropout mask come from the psave / msave
+ * a training forward left (see fbl_disent_attn_fwd; p_drop gives the scale of the kept pairs, the seed arguments are not read);
+ * besides dV, dS and dS^T it forms
+ *   dK = dS^T.Q + G2.PQ  (what fbl_disent_attn_bwd_shear computes from dS^T) -- the second term as a Toeplitz product
  * against pqx = the PQX of fbl_attn_bwd_prep (no index table, no scatter); q bf16 rows like v.  dS^T is not read back.
- * ref: autograd of model/deberta.py:789-818 and of the p2c term :896-918. */
+ * ref: autograd of model/deberta.py:789-818 (softmax, dropout, context) and of the p2c term :896-918, XSoftmax.backward
+ * :134-138, XDropout.backward :185-190. */
 int fbl_disent_attn_bwd_dspk(const void* psave, const float* msave, const void* q, int64_t ldq, const void* v, int64_t ldv,
                              const void* dO, int64_t ldo, const void* pqx, const int32_t* klen, const int32_t* border,
                              const float* lse, const float* Dv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev,

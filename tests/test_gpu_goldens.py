@@ -101,13 +101,15 @@ def test_g3_attention_stage(golden, S):
         assert (got[0, S - 5:] == 0).all()  # padded query rows: XSoftmax gives exact zeros
 
 
-@pytest.mark.parametrize("S", [37, 266])
-def test_g3b_attention_backward_stage(golden, S):
-    """The attention backward kernels (prep, dS / dV, the two shear passes, the position-table products) on the reference
-    module's inputs and a seeded upstream gradient, against the gradients the REFERENCE's own backward left on the outputs of
-    query_proj / key_proj / value_proj -- token rows: dq, dk, dv; relative-position rows: dPQ, dPK (G3b; hooks on the
-    reference module, tests/golden/make_goldens.py).  Until round 4 this stage was only checked against the builder's own
-    restatement (tests/gpu_refs.py) and, in aggregate, through the model-level gradient goldens."""
+@pytest.mark.parametrize("S,route", [(37, "recompute"), (266, "recompute"), (37, "shipped"), (266, "shipped")],
+                         ids=["37", "266", "37-shipped", "266-shipped"])
+def test_g3b_attention_backward_stage(golden, S, route):
+    """The attention backward kernels on the reference module's inputs and a seeded upstream gradient, against the gradients
+    the REFERENCE's own backward left on the outputs of query_proj / key_proj / value_proj -- token rows: dq, dk, dv;
+    relative-position rows: dPQ, dPK (G3b; hooks on the reference module, tests/golden/make_goldens.py).  route "shipped": the
+    forward saves its probabilities (NaN-filled buffers: anything read unwritten shows up) and the backward runs prep, dspk,
+    dq, pos_grad; "recompute": prep, ds, dq, the key-major shear pass, pos_grad.  Until round 4 this stage was only checked
+    against the builder's own restatement (tests/gpu_refs.py) and, in aggregate, through the model-level gradient goldens."""
     import types
 
     from frozenbilm_amd import lib as L
@@ -135,10 +137,14 @@ def test_g3b_attention_backward_stage(golden, S):
             L.gemm(kv.full, W["Wqkv"][H:], bias=W["bqkv"][H:], out_bf16=qkv[:, H:])
         ctx = torch.empty(N, H, dtype=BF16, device=DEV)
         lse = torch.empty(B, nh, S, dtype=F32, device=DEV)
+        ps = ms = None
+        if route == "shipped":
+            ps = torch.full((B, nh, Sp, Sp), float("nan"), dtype=BF16, device=DEV)
+            ms = torch.full((B, nh, Sp // 64, S), float("nan"), dtype=F32, device=DEV)
         L.disent_attn_fwd(qkv[:N, :H], qkv[:N, H:2 * H], qkv[:N, 2 * H:], qkv[N:, H:2 * H], qkv[N:, :H], eng.relidx(S),
                           run.mask_i32, 1.0 / math.sqrt(64 * 3), ctx, lse, B, S, Sp, nh, P_, klen=run.klen, border=run.border,
-                          lin=eng.lin_span)
-        sv = types.SimpleNamespace(qkv=qkv[:N], pqk=qkv[N:, : 2 * H], ctx=ctx, lse=lse, seed_att=0)
+                          lin=eng.lin_span, psave=ps, msave=ms)
+        sv = types.SimpleNamespace(qkv=qkv[:N], pqk=qkv[N:, : 2 * H], ctx=ctx, lse=lse, seed_att=0, psave=ps, msave=ms)
         dctx = dy.reshape(N, H).to(DEV).to(BF16).contiguous()
         dqkv = torch.full((N, 3 * H), float("nan"), dtype=BF16, device=DEV)
         dpqk = torch.empty(P_, 2 * H, dtype=BF16, device=DEV)
@@ -154,7 +160,7 @@ def test_g3b_attention_backward_stage(golden, S):
             ref = gb[f"{name}{tag}_{S}"].float()
             out = dpqk[:, lo:lo + H].float().cpu()
             worst[name] = (out - ref).abs().max().item() / max(ref.abs().max().item(), 1e-9)
-        print(f"G3b S={S} query_states={'yes' if tag else 'no'}: max-abs error / max |reference| per gradient: "
+        print(f"G3b route={route} S={S} query_states={'yes' if tag else 'no'}: max-abs error / max |reference| per gradient: "
               + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
         # bf16 operands (q, k, v, dO, P, dS all rounded to bf16 on the way) against the fp32 reference
         assert all(v < 3e-2 for v in worst.values()), worst

@@ -523,34 +523,32 @@ def test_head_transpose(L):
 
 
 def test_attn_bwd_prep_equals_the_separate_launches(L):
-    """fbl_attn_bwd_prep = four head transposes + rowdot in one launch: bit-identical to the stand-alone entry points"""
+    """fbl_attn_bwd_prep = two head transposes + rowdot in one launch: bit-identical to the stand-alone entry points"""
     B, S, nh, span2 = 3, 150, 4, 512
     H, Sp = nh * 64, 192
     qkv = bf(rnd(B * S, 3 * H, seed=1)).to(BF16)
     pqk = bf(rnd(span2, 2 * H, seed=2)).to(BF16)
     dO, O = bf(rnd(B * S, H, seed=3)).to(BF16), bf(rnd(B * S, H, seed=4)).to(BF16)
-    q, k, pq, pk = qkv[:, :H], qkv[:, H:2 * H], pqk[:, :H], pqk[:, H:]
+    q, pq, pk = qkv[:, :H], pqk[:, :H], pqk[:, H:]
     mk = lambda *shape: torch.full(shape, 7.0, dtype=BF16, device=DEV)
-    QT, KT, PQT, PKT = mk(nh, 64, B, Sp), mk(nh, 64, B, Sp), mk(nh, 64, span2), mk(nh, 64, span2)
+    QT, PQT = mk(nh, 64, B, Sp), mk(nh, 64, span2)
     Dv = torch.full((B, nh, S), 7.0, device=DEV)
-    L.attn_bwd_prep(q, k, pq, pk, dO, O, QT, KT, PQT, PKT, Dv, B, S, Sp, nh, span2)
-    QT2, KT2, PQT2, PKT2 = mk(nh, 64, B, Sp), mk(nh, 64, B, Sp), mk(nh, 64, span2), mk(nh, 64, span2)
+    L.attn_bwd_prep(q, pq, pk, dO, O, QT, PQT, Dv, B, S, Sp, nh, span2)
+    QT2, PQT2 = mk(nh, 64, B, Sp), mk(nh, 64, span2)
     Dv2 = torch.empty(B, nh, S, device=DEV)
     L.head_transpose(q, QT2, B, S, Sp, nh, head_major=True)
-    L.head_transpose(k, KT2, B, S, Sp, nh, head_major=True)
     L.head_transpose(pq, PQT2, 1, span2, span2, nh, head_major=False)
-    L.head_transpose(pk, PKT2, 1, span2, span2, nh, head_major=False)
     L.attn_rowdot(dO, O, Dv2, B, S, nh)
-    for a, b_, n in ((QT, QT2, "QT"), (KT, KT2, "KT"), (PQT, PQT2, "PQT"), (PKT, PKT2, "PKT"), (Dv, Dv2, "D")):
+    for a, b_, n in ((QT, QT2, "QT"), (PQT, PQT2, "PQT"), (Dv, Dv2, "D")):
         assert torch.equal(a, b_), n
     assert (QT[:, :, :, S:] == 0).all()  # positions beyond S are zero-padded
     # optional outputs: only what is asked for is written; the index-expanded tables of the fused key-major pass
     from frozenbilm_amd.model.relpos import rel_index_vector
     relidx = torch.from_numpy(rel_index_vector(S, 256, 512, 256).copy()).to(DEV)
-    KT3, PKT3, Dv3 = mk(nh, 64, B, Sp), mk(nh, 64, span2), torch.empty(B, nh, S, device=DEV)
+    Dv3 = torch.empty(B, nh, S, device=DEV)
     PQX, PKX = mk(nh, 2 * Sp, 64), mk(nh, 2 * Sp, 64)
-    L.attn_bwd_prep(q, k, pq, pk, dO, O, None, KT3, None, PKT3, Dv3, B, S, Sp, nh, span2, relidx=relidx, PQX=PQX, PKX=PKX)
-    assert torch.equal(KT3, KT2) and torch.equal(PKT3, PKT2) and torch.equal(Dv3, Dv2)
+    L.attn_bwd_prep(q, pq, pk, dO, O, None, None, Dv3, B, S, Sp, nh, span2, relidx=relidx, PQX=PQX, PKX=PKX)
+    assert torch.equal(Dv3, Dv2)
     t = torch.arange(2 * Sp, device=DEV)
     rows = relidx[(t - Sp + S - 1).clamp(0, 2 * S - 2)].long()  # table row of delta = t - Sp
     for X, tab, n in ((PQX, pq, "PQX"), (PKX, pk, "PKX")):
@@ -734,13 +732,18 @@ def test_attention_fwd_dropout_rate(L):
 @pytest.mark.parametrize("saved_p", [False, True, "gt_route", "separate_dk"], ids=["recompute", "saved_p", "gt_route", "separate_dk"])
 @pytest.mark.parametrize("B,S,nh", [(1, 16, 1), (2, 37, 2), (2, 130, 2), (2, 266, 2), (3, 266, 1), (2, 512, 1), (4, 200, 2)])
 def test_attention_bwd(L, B, S, nh, saved_p):
-    """saved_p: kernel A reads the un-normalised probabilities the (training) forward left in HBM (fbl_disent_attn_bwd_dsp)
-    instead of recomputing the scores; the forward then runs with the same klen / border as the backward (it writes exactly
-    the tile pairs the backward reads -- the buffers start NaN-filled)."""
-    from frozenbilm_amd.attn_bwd import disent_attn_bwd
+    """saved_p: kernel A reads the un-normalised probabilities the (training) forward left in HBM and forms dK in place
+    (fbl_disent_attn_bwd_dspk) instead of recomputing the scores (fbl_disent_attn_bwd_ds + the key-major shear pass); the
+    forward then runs with the same klen / border as the backward (it writes exactly the tile pairs the backward reads -- the
+    buffers start NaN-filled).
+    gt_route: the recompute route, and its position-table gradients (fbl_attn_pos_grad) also against their G^T formulation
+    dPK = G1^T.Q, dPQ = G2^T.K, formed in torch from the dS / dS^T the kernels wrote (tighter bound: same dS on both sides).
+    separate_dk: the saved-P route, and dK also by the separate key-major shear pass from the dS^T that the saved-P kernel A
+    wrote (that dS^T is otherwise only seen through dPQ)."""
+    from frozenbilm_amd.attn_bwd import disent_attn_bwd, pos_table_grads
 
     qkv, pqk, mask, relidx, H = _attn_inputs(B, S, nh, seed=20 + S)
-    if B >= 3:  # short samples: whole 64-row steps of G^T beyond klen stay unwritten and must be skipped downstream
+    if B >= 3:  # short samples: whole 64-row tiles beyond klen stay unwritten and must be skipped downstream
         mask[1, 70:] = 0
         mask[2, 33:] = 0
     if S == 512:
@@ -748,8 +751,7 @@ def test_attention_bwd(L, B, S, nh, saved_p):
     qkv = (qkv.float() * 0.5).to(BF16)
     pqk = (pqk.float() * 0.5).to(BF16)
     klen_t = _klen(mask) if S > 100 else None  # exercise both the dense and the tile-skipping paths
-    gt_route = saved_p == "gt_route"  # position-table gradients through G^T + split-K GEMMs (rounds 1-5) instead of fbl_attn_pos_grad
-    separate_dk = saved_p == "separate_dk"  # saved probabilities, dK by the key-major shear pass instead of inside kernel A
+    gt_route, separate_dk = saved_p == "gt_route", saved_p == "separate_dk"
     saved_p = saved_p is True or separate_dk
     saved = [] if saved_p else None
     ctx, lse = _run_attn_fwd(L, qkv, pqk, mask, relidx, B, S, nh, klen=klen_t, save_p=saved)
@@ -772,18 +774,20 @@ def test_attention_bwd(L, B, S, nh, saved_p):
     import types as _t
     eng.cfg = _t.SimpleNamespace(position_buckets=256, max_rel=512, att_span=256)  # enables the relidx-range / injective-store paths
     run.B, run.S, run.mask_i32, run.p_att = B, S, mask.view(-1), 0.0
-    eng.pos_grad_gt = gt_route
-    eng.attn_fused_dk = eng.attn_toeplitz_dq = not separate_dk  # "separate_dk": both shear passes of rounds 1-5
     run.klen = klen_t
     run.border = _border(run.klen) if (run.klen is not None and B >= 3) else None  # longest-first dispatch (XCD-aware map at B=4)
-    import frozenbilm_amd.attn_bwd as AB
-    AB.POISON_GT = True  # unwritten G^T blocks hold NaN: the position-table GEMMs must skip exactly those
     sv.qkv, sv.pqk, sv.ctx, sv.lse, sv.seed_att = qkv, pqk, ctx, lse, 0
     if saved_p:
         sv.psave, sv.msave = saved
     dqkv = torch.zeros(B * S, 3 * H, dtype=BF16, device=DEV)
     dpqk = torch.zeros(pqk.shape[0], 2 * H, dtype=BF16, device=DEV)
-    disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk)
+    st = None
+    if gt_route or separate_dk:  # keep dS / dS^T: the position-table gradients run right behind, as defer_pos=False does
+        st = disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk, defer_pos=True)
+        dpos = pos_table_grads(eng, st)
+        dpqk.copy_(dpos)
+    else:
+        disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk)
     gq = qkvf.grad
     sc = gq.abs().max().item()
     for name, sl in (("dQ", slice(0, H)), ("dK", slice(H, 2 * H)), ("dV", slice(2 * H, 3 * H))):
@@ -791,6 +795,37 @@ def test_attention_bwd(L, B, S, nh, saved_p):
     sp = pqkf.grad.abs().max().item()
     close(dpqk[:, H:], pqkf.grad[:, H:], 3e-2, 2e-2 * sp, "dPK")
     close(dpqk[:, :H], pqkf.grad[:, :H], 3e-2, 2e-2 * sp, "dPQ")
+    span2 = pqk.shape[0]
+    kl = klen_t.tolist() if klen_t is not None else [S] * B
+    if gt_route:
+        # G1[b,h,i,r] = sum_{j: idx(i-j) = r} dS[i,j],  G2[b,h,j,r] = sum_{i: idx(i-j) = r} dS[i,j]; only the [klen x klen] corner
+        # of dS / dS^T is written (and non-zero)
+        ii = torch.arange(S, device=DEV)
+        R = relidx.long()[ii[:, None] - ii[None, :] + S - 1]  # [i, j] -> table row
+        live = torch.zeros(B, 1, S, S, dtype=torch.bool, device=DEV)
+        for b in range(B):
+            live[b, :, :kl[b], :kl[b]] = True
+        dS = torch.where(live, st["dS"][:, :, :S, :S].float(), 0.0)  # (outside the corner: unwritten memory)
+        dST = torch.where(live, st["dST"][:, :, :S, :S].float(), 0.0)
+        G1 = torch.zeros(B, nh, S, span2, device=DEV).scatter_add_(3, R.expand(B, nh, S, S), dS)
+        G2 = torch.zeros(B, nh, S, span2, device=DEV).scatter_add_(3, R.t().expand(B, nh, S, S), dST)
+        qh, kh = (qkv[:, i * H:(i + 1) * H].float().view(B, S, nh, 64).permute(0, 2, 1, 3) for i in range(2))
+        # G rounded to bf16 like the kernel's MFMA operand
+        g_pk = torch.einsum("bhir,bhid->rhd", G1.to(BF16).float(), qh).reshape(span2, H)
+        g_pq = torch.einsum("bhjr,bhjd->rhd", G2.to(BF16).float(), kh).reshape(span2, H)
+        sg = max(g_pk.abs().max().item(), g_pq.abs().max().item())
+        close(dpos[:, H:], g_pk, 1e-2, 2e-3 * sg, "dPK vs G1^T.Q")
+        close(dpos[:, :H], g_pq, 1e-2, 2e-3 * sg, "dPQ vs G2^T.K")
+    if separate_dk:
+        Sp = (S + 63) // 64 * 64
+        QT = torch.empty(nh, 64, B, Sp, dtype=BF16, device=DEV)
+        PQT = torch.empty(nh, 64, span2, dtype=BF16, device=DEV)
+        L.head_transpose(qkv[:, :H], QT, B, S, Sp, nh, head_major=True)
+        L.head_transpose(pqk[:, :H], PQT, 1, span2, span2, nh, head_major=False)
+        dK2 = torch.full((B * S, H), float("nan"), dtype=BF16, device=DEV)
+        L.disent_attn_bwd_shear(st["dST"], QT, PQT, relidx, dK2, B, S, Sp, nh, span2, klen=klen_t, lin=128, border=run.border)
+        close(dK2, gq[:, H:2 * H], 3e-2, 2e-2 * sc, "dK (shear pass)")
+        close(dK2, dqkv[:, H:2 * H], 2e-2, 1e-2 * sc, "dK (shear pass) vs dK (dspk)")
 
 
 def _attn_bwd_call(L, qkv, pqk, ctx, lse, dctx, mask, relidx, B, S, nh, H, p_att, seed, saved=None):

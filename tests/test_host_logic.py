@@ -43,6 +43,24 @@ class Tok:
         return 4
 
 
+def test_position_gradient_delta_lists_stay_within_the_kernel_limit():
+    """fbl_attn_pos_grad takes at most 8 relative positions per table row.  The FrozenBiLM bucket map (256 buckets, 512
+    positions) stays within it at every sequence length; a map beyond it is refused on the host, before any launch."""
+    from frozenbilm_amd.attn_bwd import _delta_ranges
+
+    cpu = torch.device("cpu")
+    ours = types.SimpleNamespace(position_buckets=256, max_rel=512, att_span=256)
+    worst = 0
+    for S in range(1, 513):
+        dlo, dcnt, cmax = _delta_ranges(S, ours, cpu)
+        assert cmax <= 8 and cmax == int(dcnt.max()) and dlo.dtype == torch.int16, S
+        worst = max(worst, cmax)
+    assert worst == 6
+    coarse = types.SimpleNamespace(position_buckets=64, max_rel=512, att_span=64)
+    with pytest.raises(NotImplementedError, match=r"at most 8 .*position_buckets=64, max_relative_positions=512 at sequence length 512"):
+        _delta_ranges(512, coarse, cpu)
+
+
 def test_mask_tokens_get_mask_lr_bit_exact(golden):
     g = golden("G7_misc")
     assert torch.equal(misc.get_mask(g["video_len"], 10), g["get_mask"])
