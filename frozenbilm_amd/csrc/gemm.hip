@@ -10,8 +10,6 @@
 // address (LDS-DMA destinations are lane-linear) and again on the ds_read_b128 side -> conflict-free fragment reads.
 // MFMA operands are swapped (weights as "A", activations as "B") so each lane owns 4 consecutive output columns
 // -> 16-byte fp32 / 8-byte bf16 epilogue stores.
-#include <stdlib.h>
-
 #include "gemm_common.h"
 
 using namespace fblgemm;
@@ -29,23 +27,22 @@ template <int NW> struct TileCfg {
   static constexpr int SMEM_BYTES = (NW * 64 * 68 * 4 > 2 * STAGE_BYTES) ? NW * 64 * 68 * 4 : 2 * STAGE_BYTES;
 };
 
-// MI_: 16-row MFMA tiles per wave along M.  The tile is (32*MI_) x (32*NW); MI_ = NW gives the square 128/256 tiles,
-// MI_ = 7 with NW = 8 a 224x256 tile for shapes whose 256x256 grid leaves CUs idle (8512 rows = 38 x 224 exactly:
+// MI: 16-row MFMA tiles per wave along M.  The tile is (32*MI) x (32*NW); MI = NW gives the square 128/256 tiles,
+// MI = 7 with NW = 8 a 224x256 tile for shapes whose 256x256 grid leaves CUs idle (8512 rows = 38 x 224 exactly:
 // 228 tiles on 256 CUs for N = 1536 instead of 204 bigger ones).  LDS keeps the 32*NW-row A image; the unused rows are
 // simply not fetched.
-template <int NW, int ACT, int AUX, bool SPLITK, int SCHED = 0, int MI_ = NW>
-__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(GemmArgs g) {
+// RING: the 3-stage ring main loop of the tall, narrow problems (MI = 2, NW = 4: 64x128 tiles) instead of the 2-stage loop.
+template <int NW, int ACT, int AUX, bool SPLITK, bool RING, int MI>
+__global__ __launch_bounds__(NW * 64, 2) void gemm_bf16_nt_kernel(GemmArgs g) {
   using Cfg = TileCfg<NW>;
-  constexpr int MI = MI_;           // 16-row MFMA tiles per wave along M; 4 tiles (64 cols) along N
   constexpr int BM = 32 * MI;
-  // LDS stage = A image | B image.  The 2-stage loops reserve the square tile's A image even for shorter tiles; the
-  // ring of SCHED 5 packs the BM rows it really has (three stages of 24 KiB: two workgroups per CU still fit)
+  // LDS stage = A image | B image.  The 2-stage loop reserves the square tile's A image even for shorter tiles; the
+  // ring packs the BM rows it really has (three stages of 24 KiB: two workgroups per CU still fit)
   constexpr int BN = Cfg::BN;
-  constexpr int TILE_BYTES = (SCHED == 5) ? BM * BK * 2 : Cfg::TILE_BYTES;
-  constexpr int STAGE_BYTES = (SCHED == 5) ? TILE_BYTES + Cfg::TILE_BYTES : Cfg::STAGE_BYTES;
+  constexpr int TILE_BYTES = RING ? BM * BK * 2 : Cfg::TILE_BYTES;
+  constexpr int STAGE_BYTES = RING ? TILE_BYTES + Cfg::TILE_BYTES : Cfg::STAGE_BYTES;
   constexpr int WC = NW / 2;        // waves along N (2 rows of waves along M)
   constexpr int WROWS = MI * 16;    // rows of C per wave
-  static_assert(SCHED == 0 || SCHED == 5 || MI_ == NW, "the counted-vmcnt schedules assume the square tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages x (A tile | B tile)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -116,31 +113,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(
 #pragma unroll
     for (int i = 0; i < MI; ++i) af[i] = *(const bf16x8*)(base + a_off0 + i * 2048 + pc);
   };
-  if constexpr (NW == 8 && (SCHED == 1 || SCHED == 4)) {
-    // ---- counted-vmcnt schedule: every tile is requested TWO K-steps before it is consumed (raw s_barrier +
-    // explicit s_waitcnt: __syncthreads() would drain the in-flight DMA).
-    issue(kt0, 0);
-    if (kt0 + 1 < kt1) issue(kt0 + 1, 1);
-    for (int kt = kt0; kt < kt1; ++kt) {
-      const int stage = (kt - kt0) & 1;
-      const char* base = smem + stage * STAGE_BYTES;
-      if (kt + 1 < kt1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      bf16x8 af0[MI], bf0[4], af1[MI], bf1[4];
-      read_frags(base, 0, af0, bf0);
-      if constexpr (SCHED == 1) mfma_block(af0, bf0);
-      read_frags(base, 1, af1, bf1);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every fragment of this stage is in registers
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (kt + 2 < kt1) issue(kt + 2, stage);
-      if constexpr (SCHED == 4) mfma_block(af0, bf0);
-      mfma_block(af1, bf1);
-    }
-    __builtin_amdgcn_s_barrier();  // all LDS tile reads retired before the epilogue reuses the memory
-  } else if constexpr (SCHED == 5) {
+  if constexpr (RING) {
     // ---- ring of NS = 3 stages for the tall, narrow problems (adapter bottleneck projections: about one 64x128 workgroup
     // per CU, so nothing else on the CU hides a load): two K-steps of operands in flight, ONE raw barrier per K-step.
     //   iteration kt:  wait until stage kt has landed (one younger stage may stay in flight) -> barrier (every wave's part
@@ -169,30 +142,20 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 2) void gemm_bf16_nt_kernel(
     }
     __builtin_amdgcn_s_barrier();  // all LDS tile reads retired before the epilogue reuses the memory
   } else {
-  issue(kt0, 0);
-  __syncthreads();  // drains the LDS-DMA (vmcnt(0)) and publishes stage 0
-  for (int kt = kt0; kt < kt1; ++kt) {
-    const int stage = (kt - kt0) & 1;
-    if (kt + 1 < kt1) issue(kt + 1, stage ^ 1);
-    const char* base = smem + stage * STAGE_BYTES;
-    if constexpr (SCHED == 2) {  // all 24 fragment reads first, then 64 MFMAs
-      bf16x8 af0[MI], bf0[4], af1[MI], bf1[4];
-      read_frags(base, 0, af0, bf0);
-      read_frags(base, 1, af1, bf1);
-      mfma_block(af0, bf0);
-      mfma_block(af1, bf1);
-    } else {
+    issue(kt0, 0);
+    __syncthreads();  // drains the LDS-DMA (vmcnt(0)) and publishes stage 0
+    for (int kt = kt0; kt < kt1; ++kt) {
+      const int stage = (kt - kt0) & 1;
+      if (kt + 1 < kt1) issue(kt + 1, stage ^ 1);
+      const char* base = smem + stage * STAGE_BYTES;
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         bf16x8 af[MI], bfg[4];
         read_frags(base, s, af, bfg);
-        if constexpr (SCHED == 3) __builtin_amdgcn_s_setprio(1);
         mfma_block(af, bfg);
-        if constexpr (SCHED == 3) __builtin_amdgcn_s_setprio(0);
       }
+      __syncthreads();
     }
-    __syncthreads();
-  }
   }
 
   // ---- epilogue (gemm_common.h): slabs of 64 rows of this wave's tile through a wave-private LDS staging tile
@@ -301,26 +264,25 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(GemmTnArgs g) {
 }
 
 // 256x256 (or 224x256) tiles only where both dimensions fill them and the grid still covers half the chip
+// (M >= 512 with a very wide N: the vocabulary GEMM of the loss on the labelled rows, [~700 x 128100 x 1536] -- 3 x 501 big tiles)
 static inline bool big_tile_shape(int M, int N, int batch) {
-  // (M >= 512 with a very wide N: the vocabulary GEMM of the loss on the labelled rows, [~700 x 128100 x 1536] -- 3 x 501 big tiles)
-  static const int wide = FBL_ENV_INT("FBL_GEMM_WIDE", 1);
-  return batch == 1 && (M >= 2048 || (wide && M >= 512 && N >= 16384)) && N >= 1024 &&
+  return batch == 1 && (M >= 2048 || (M >= 512 && N >= 16384)) && N >= 1024 &&
          ((long)((M + 255) / 256) * ((N + 255) / 256) >= 128);
 }
 
 constexpr double FBL_R128_US_PER_KTILE = 0.86;  // 128-row 8-phase tile: time per K-tile of one workgroup (measured: [5322,1536,6144] 88 us)
 
+// CUs of the device that is current at the first call (256 if the query fails)
 static int device_cu_count() {
-  static int n_cu = 0;
-  if (!n_cu) {
+  static const int n_cu = [] {
     int dev = 0;
     hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+      return prop.multiProcessorCount;
+    return 256;
+  }();
   return n_cu;
 }
-
 
 // out[b][m][n] += sum_ks ws[b][ks][m][n]   (deterministic split-K fold)
 __global__ void splitk_reduce_kernel(const float* ws, int splitk, int M, int N, int Nw, float* out, long ldc, long sC) {
@@ -381,276 +343,134 @@ static bool fork_join_events(hipStream_t s, hipStream_t aux, hipEvent_t* fork, h
   return true;
 }
 
-// residual operand of the adapter-tail epilogue (fbl_adapter_up_resid_fwd)
-struct TailArgs {
-  const float* r_t; int64_t ld_r; const float* r_stats; const float* r_gamma; const float* r_beta; const int32_t* r_rowmask;
+// ---- dispatch of the NT GEMM: a pure plan (which kernel runs which rows on which stream) and the launcher that executes it
+
+// What runs one launch, and its tile (rows x columns)
+enum GemmKernel {
+  G8_256, G8_224, G8_128,  // 8-phase kernel (gemm8.hip), 256 columns
+  G8_SPLITK,               // 8-phase 256x256 tiles, K cut into slices of GemmPlan::k8_per K-tiles, partials to the workspace
+  T2_256, T2_224,          // 2-stage kernel, 8 waves, 256 columns
+  T2_128, T2_64_RING,      // 2-stage kernel, 4 waves, 128 columns (the 64-row tiles run the 3-stage ring)
+  T2_128_SPLITK,           // 2-stage 128x128 tiles, partials to the workspace or atomically added to C
+};
+static int tile_rows(GemmKernel k) {
+  switch (k) {
+    case G8_224: case T2_224: return 224;
+    case G8_128: case T2_128: case T2_128_SPLITK: return 128;
+    case T2_64_RING: return 64;
+    default: return 256;
+  }
+}
+static int tile_cols(GemmKernel k) { return (k == T2_128 || k == T2_64_RING || k == T2_128_SPLITK) ? 128 : 256; }
+
+struct GemmLaunch {
+  GemmKernel kernel;
+  int row0, rows;  // rows [row0, row0 + rows) of C
+  int tiles_m, tiles_n;
+  dim3 grid;
+  bool on_aux;     // on the caller's aux stream: forked from `stream` before, joined back into it after the launches
 };
 
-// p_drop > 0 (ReLU epilogue only): dropout of the activated output, element (m, n) keyed by (drop_seed, m*ldc + n)
-static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
-                        const float* bias, const float* rowscale, float alpha, int act, int aux_kind,
-                        const void* aux, int64_t ld_aux, float* out_f32, void* out_bf16, void* out_pre_bf16,
-                        int64_t ldc, int batch, int64_t strideA, int64_t strideB, int64_t strideC,
-                        int64_t strideAux, int64_t strideBias, int splitk, float* splitk_ws,
-                        int64_t splitk_ws_floats, float p_drop, uint64_t drop_seed, void* stream, int seg_n = 0,
-                        void* seg_out = nullptr, int64_t seg_ld = 0, int64_t drop_row0 = 0, void* aux_stream = nullptr,
-                        const TailArgs* tail = nullptr, const uint64_t* drop_seed_dev = nullptr) {
-  if (M <= 0 || N <= 0 || batch <= 0) return 0;
-  if ((aux_kind == FBL_AUX_ADAPTER_TAIL) != (tail != nullptr)) return FBL_ERR_ARG;
-  if (K <= 0 || (K % BK) != 0) return FBL_ERR_SHAPE;           // K must be a multiple of 64 (callers zero-pad)
-  if ((lda % 8) != 0 || (ldb % 8) != 0) return FBL_ERR_ALIGN;  // 16-byte operand rows
-  if (splitk < 1) splitk = 1;
-  const bool accumulate = splitk > 1;  // callers ask for splitk >= 2 when they want "out += A.B^T"
-  if (splitk > 1) {  // every split must own at least one K tile
-    const int nk = K / BK;
-    const int per = (nk + splitk - 1) / splitk;
-    splitk = (nk + per - 1) / per;
-  }
-  const int Nw = (N + 3) & ~3;
-  if (accumulate && splitk_ws && (int64_t)batch * splitk * M * Nw > splitk_ws_floats) splitk_ws = nullptr;  // too small
-  if (accumulate && bias && splitk_ws) return FBL_ERR_ARG;
-  if (accumulate && (!out_f32 || out_bf16 || out_pre_bf16 || act != FBL_ACT_NONE || aux_kind != FBL_AUX_NONE))
-    return FBL_ERR_ARG;  // split-K only accumulates (atomicAdd) into a pre-initialised fp32 output
-  if (!out_f32 && !out_bf16) return FBL_ERR_ARG;
-  GemmArgs g;
-  g.A = (const bf16*)A; g.B = (const bf16*)B; g.lda = lda; g.ldb = ldb;
-  g.M = M; g.N = N; g.K = K;
-  g.bias = bias; g.rowscale = rowscale; g.alpha = alpha; g.act = act; g.aux_kind = aux_kind;
-  g.aux = aux; g.ld_aux = ld_aux;
-  g.out_f32 = out_f32; g.out_bf16 = (bf16*)out_bf16; g.out_pre = (bf16*)out_pre_bf16; g.ldc = ldc;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sAux = strideAux; g.sBias = strideBias;
-  g.splitk = splitk;
-  g.k8_per = 0;
-  g.ws = accumulate ? splitk_ws : nullptr;
-  g.Nw = Nw;
-  g.drop_thresh = 0; g.drop_seed = drop_seed; g.drop_seed_dev = drop_seed_dev; g.drop_inv_keep = 1.f; g.drop_ld = ldc;
-  g.seg_n = seg_n; g.seg_out = (bf16*)seg_out; g.seg_ld = seg_ld; g.drop_row0 = drop_row0;
-  g.r_t = nullptr; g.ld_r = 0; g.r_stats = nullptr; g.r_gamma = nullptr; g.r_beta = nullptr; g.r_rowmask = nullptr;
-  if (tail) {
-    if (accumulate || batch != 1 || seg_n > 0 || !out_f32 || out_bf16 || out_pre_bf16 || act != FBL_ACT_NONE || rowscale ||
-        !aux || !tail->r_t || (N & 3) || (ldc & 3) || (ld_aux & 3) || (tail->ld_r & 3) ||
-        (tail->r_stats && (!tail->r_gamma || !tail->r_beta)))
-      return FBL_ERR_ARG;
-    g.r_t = tail->r_t; g.ld_r = tail->ld_r; g.r_stats = tail->r_stats; g.r_gamma = tail->r_gamma; g.r_beta = tail->r_beta;
-    g.r_rowmask = tail->r_rowmask;
-    g.drop_ld = N;  // keys of fbl_ln_fwd: (seed, m*H + n)
-  }
-  if (seg_n > 0) {
-    // The epilogue branches per LANE on "column >= seg_n" but stages accumulators through per-WAVE LDS patches that all 64
-    // lanes fill: the segment boundary must not cut a wave's column range.  A wave of the 2-stage kernels owns 64
-    // contiguous columns, a wave of the 256-wide tiles (2-stage and 8-phase) two 32-column ranges 128 apart -> the
-    // boundary has to be a multiple of 64, and of 256 for the wide tiles (otherwise the narrow tiles take the problem).
-    if ((seg_n & 63) || seg_n >= N || !seg_out || accumulate || batch != 1) return FBL_ERR_ARG;
-    g.drop_ld = seg_ld;
-  }
-  if (p_drop > 0.f) {
-    if ((act != FBL_ACT_RELU && seg_n <= 0 && !tail) || p_drop >= 1.f || batch != 1) return FBL_ERR_ARG;
-    g.drop_thresh = fbl_drop_thresh(p_drop);
-    g.drop_inv_keep = 1.f / (1.f - p_drop);
-  }
+struct GemmPlan {
+  GemmLaunch launch[2];  // in launch order
+  int n;
+  int splitk, k8_per;    // K slices of every launch (G8_SPLITK: its own slicing, k8_per K-tiles per slice)
+  bool fold;             // splitk_reduce_kernel folds the workspace into C after the launches
+  bool big8;             // the big-tile route on the 8-phase kernel (what fbl_gemm_plan reports)
+};
+
+// What the planner needs to know about a call besides its validated GemmArgs
+struct GemmCall {
+  int batch;
+  bool accumulate;     // C += A.B^T (split-K)
+  bool dropout;        // p_drop > 0
+  bool ws_given;       // the caller passed a split-K workspace pointer, used or not
+  int64_t ws_floats;   // its size
+  bool aux_stream;     // a second stream, distinct from `stream`, is available
+  int n_cu;
+};
+
+// Pure host logic: no HIP call, no launch.
+static GemmPlan plan_gemm(const GemmArgs& g, const GemmCall& c) {
+  const int M = g.M, N = g.N, nk = g.K / BK, n_cu = c.n_cu;
+  const bool tail = g.aux_kind == FBL_AUX_ADAPTER_TAIL;
+  GemmPlan p{};
+  p.splitk = g.splitk;
+  p.fold = c.accumulate && g.ws;
+  auto add = [&](GemmKernel k, int row0, int rows, bool on_aux) {
+    const int tm = (rows + tile_rows(k) - 1) / tile_rows(k), tn = (N + tile_cols(k) - 1) / tile_cols(k);
+    p.launch[p.n++] = GemmLaunch{k, row0, rows, tm, tn, dim3(tm * tn, c.batch * p.splitk), on_aux};
+  };
+
   // big tiles only where both dimensions fill them and the grid still covers the chip
-  static const int force_small = FBL_ENV_INT("FBL_GEMM_SMALL", 0);
-  const bool big = !force_small && !accumulate && (p_drop <= 0.f || seg_n > 0 || tail) && (seg_n <= 0 || (seg_n & 255) == 0) &&
-                   big_tile_shape(M, N, batch);
-  // A multi-round problem of the 8-phase kernel whose partial last round still uses a good part of the chip (96..192 of 256
-  // CUs; the QKV projection [9024,4608,1536]: 648 tiles of 256 rows, 738 of 224) runs as ONE plain launch instead of "whole
-  // rounds + 128x128 remainder" (122 us as 224-row tiles; the split: 146).  With a nearly empty last round (FFN-up: 816
-  // tiles, 48 left) the split stays better: an epilogue costs a CU 10-20 us of VALU / store time that nothing on that CU
-  // overlaps, so a fourth round of full tiles (222 us) loses to three rounds plus small tiles (208 us).
-  // (Rounds 2-3 delayed part of the first round by a spin-wait on the real-time clock to take the CUs out of lockstep: worth
-  //  13 us on the 256-row launch, nothing on the 224-row one the problem takes now -- removed.)
-  static const int gemm8_on = FBL_ENV_INT("FBL_GEMM8", 3);
-  bool single_launch = false;
-  if (big && splitk_ws_floats >= 0 && gemm8_on > 0 && gemm8_eligible(g)) {
-    const long total = (long)((N + 255) / 256) * ((M + 255) / 256);
-    const long rem = total % 256;
-    single_launch = total > 256 && rem >= 96 && rem <= 192;
-  }
-  if (big && splitk_ws_floats >= 0 && !single_launch && !tail) {  // (negative values mark the two halves of an already split launch)
-    // Wave quantisation: one 256x256 workgroup per CU, so a grid of T tiles costs ceil(T/CUs) rounds.  When the last
-    // round would be mostly empty, give the big tiles only as many M rows as fill whole rounds and run the remaining
-    // rows with the 128x128 configuration (2 workgroups/CU, 1/4 of the work per tile) right behind.
-    static int n_cu = 0;
-    if (!n_cu) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-      if (n_cu <= 0) n_cu = 256;
+  const bool big = !c.accumulate && (!c.dropout || g.seg_n > 0 || tail) && (g.seg_n <= 0 || g.seg_n % 256 == 0) &&
+                   big_tile_shape(M, N, c.batch);
+  p.big8 = big && gemm8_eligible(g);
+  if (big) {
+    const long tn = (N + 255) / 256, t256 = tn * ((M + 255) / 256);
+    // A multi-round problem of the 8-phase kernel whose partial last round still uses a good part of the chip (96..192 of 256
+    // CUs; the QKV projection [9024,4608,1536]: 648 tiles of 256 rows, 738 of 224) runs as ONE plain launch instead of "whole
+    // rounds + 128x128 remainder" (122 us as 224-row tiles; the split: 146).  With a nearly empty last round (FFN-up: 816
+    // tiles, 48 left) the split stays better: an epilogue costs a CU 10-20 us of VALU / store time that nothing on that CU
+    // overlaps, so a fourth round of full tiles (222 us) loses to three rounds plus small tiles (208 us).
+    // (Rounds 2-3 delayed part of the first round by a spin-wait on the real-time clock to take the CUs out of lockstep: worth
+    //  13 us on the 256-row launch, nothing on the 224-row one the problem takes now -- removed.)
+    const bool single_launch = p.big8 && t256 > 256 && t256 % 256 >= 96 && t256 % 256 <= 192;
+    // Wave quantisation: one 256x256 workgroup per CU, so a grid of T tiles costs ceil(T/CUs) rounds.  When the last round
+    // would be less than 2/3 full, give the big tiles only as many M rows as fill whole rounds and run the remaining rows on
+    // small tiles (64x128 when their 128x128 grid would leave CUs idle: 320 rows x 6144 -> 240 workgroups instead of 144).
+    // The remainder runs on the caller's aux stream (if one is given), launched BEFORE the big tiles: its workgroups take their
+    // CUs first, so those CUs reach their first big tile a fraction of a tile late -- the chip leaves lockstep (the epilogue of
+    // a round is an HBM burst: every CU stores its tile at the same moment while the memory system idles during the main
+    // loops) and the remainder costs no round of its own.  Without an aux stream it simply precedes the big tiles.
+    // (A call that passes a workspace pointer is never split.)
+    const long rem = t256 % n_cu;
+    const int m_big = (int)((t256 - rem) / tn) * 256;  // whole rounds worth of M tiles
+    if (!single_launch && !tail && !c.ws_given && t256 > n_cu && rem != 0 && rem * 3 < (long)n_cu * 2 && m_big >= 256 &&
+        m_big < M && M - m_big >= 64) {
+      const int m_rem = M - m_big;
+      add((long)((m_rem + 127) / 128) * ((N + 127) / 128) < 200 ? T2_64_RING : T2_128, m_big, m_rem, c.aux_stream);
+      GemmArgs gb = g;
+      gb.M = m_big;
+      // (the whole rounds keep their 256-row tiles only if their own shape still asks for big tiles)
+      const GemmKernel k = !big_tile_shape(m_big, N, 1) ? T2_128
+                           : (gemm8_eligible(gb) && gemm8_supports(g.act, g.aux_kind, 256)) ? G8_256 : T2_256;
+      add(k, 0, m_big, false);
+      return p;
     }
-    const int tn = (N + 255) / 256, tm = (M + 255) / 256;
-    const long total = (long)tn * tm;
-    const long rem = total % n_cu;
-    if (total > n_cu && rem != 0 && rem * 3 < (long)n_cu * 2) {  // last round less than 2/3 full
-      const int tm_big = (int)((total - rem) / tn);             // whole rounds worth of M tiles
-      const int m_big = tm_big * 256;
-      if (tm_big >= 1 && m_big < M && M - m_big >= 64 && !splitk_ws) {
-        // The remainder rows run on the CALLER's aux_stream (if one is given), launched BEFORE the big tiles and forked
-        // from / joined back into `stream` by events: its workgroups take their CUs first, so those CUs reach their first
-        // big tile a fraction of a tile late -- the chip leaves lockstep (the epilogue of a round is an HBM burst: every CU
-        // stores its tile at the same moment while the memory system idles during the main loops) and the remainder costs
-        // no round of its own.  Without an aux stream the remainder simply precedes the big tiles on `stream`.
-        // FBL_GEMM_REM (debug builds) bit 0: use the aux stream; bit 1: remainder in 64x128 tiles (320 rows x 6144: 240
-        // workgroups instead of 144).
-        static const int rem_mode = FBL_ENV_INT("FBL_GEMM_REM", 3);
-        bool forked = false;
-        hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-        void* s_rem = stream;
-        if ((rem_mode & 1) && aux_stream && aux_stream != stream) {
-          if (!fork_join_events((hipStream_t)stream, (hipStream_t)aux_stream, &ev_fork, &ev_join)) return FBL_ERR_ARG;
-          if (hipEventRecord(ev_fork, (hipStream_t)stream) != hipSuccess) return FBL_ERR_ARG;
-          if (hipStreamWaitEvent((hipStream_t)aux_stream, ev_fork, 0) != hipSuccess) return FBL_ERR_ARG;
-          s_rem = aux_stream;
-          forked = true;
-        }
-        const size_t aux_es = (aux_kind == FBL_AUX_ADD_F32) ? 4 : 2;
-        int rc = gemm_nt_impl((const char*)A + (size_t)m_big * lda * 2, lda, B, ldb, M - m_big, N, K, bias,
-                              rowscale ? rowscale + m_big : nullptr, alpha, act, aux_kind,
-                              aux ? (const char*)aux + (size_t)m_big * ld_aux * aux_es : nullptr, ld_aux,
-                              out_f32 ? out_f32 + (size_t)m_big * ldc : nullptr,
-                              out_bf16 ? (char*)out_bf16 + (size_t)m_big * ldc * 2 : nullptr,
-                              out_pre_bf16 ? (char*)out_pre_bf16 + (size_t)m_big * ldc * 2 : nullptr, ldc, 1, 0, 0, 0, 0, 0,
-                              1, nullptr, (rem_mode & 2) ? -3 : -2, p_drop, drop_seed, s_rem, seg_n,
-                              seg_out ? (char*)seg_out + (size_t)m_big * seg_ld * 2 : nullptr, seg_ld, drop_row0 + m_big, nullptr,
-                              nullptr, drop_seed_dev);
-        if (rc) return rc;
-        if (forked && hipEventRecord(ev_join, (hipStream_t)aux_stream) != hipSuccess) return FBL_ERR_ARG;
-        rc = gemm_nt_impl(A, lda, B, ldb, m_big, N, K, bias, rowscale, alpha, act, aux_kind, aux, ld_aux, out_f32,
-                          out_bf16, out_pre_bf16, ldc, 1, 0, 0, 0, 0, 0, 1, nullptr, -1, p_drop, drop_seed, stream, seg_n, seg_out, seg_ld, drop_row0, nullptr, nullptr, drop_seed_dev);
-        if (rc) return rc;
-        if (forked && hipStreamWaitEvent((hipStream_t)stream, ev_join, 0) != hipSuccess) return FBL_ERR_ARG;
-        return 0;
-      }
-    }
+    // 224x256 tiles when they cover the problem in fewer (rounds x tile area) than 256x256 -- the N = 1536 GEMMs of the
+    // step: 38 x 6 = 228 tiles in one round instead of 204 tiles that are 14 % bigger.  The 8-phase kernel takes the launch at
+    // the first height that instantiates the epilogue (measured: [8512,1536,6144] 915 -> 1139 TFLOP/s as 256x256 8-phase
+    // tiles, although only 204 of 256 CUs get one; more as 224x256).
+    const long t224 = tn * ((M + 223) / 224);
+    const bool r224 = ((t224 + n_cu - 1) / n_cu) * 224 * 100 < ((t256 + n_cu - 1) / n_cu) * 256 * 97;
+    if (p.big8 && r224 && gemm8_supports(g.act, g.aux_kind, 224)) add(G8_224, 0, M, false);
+    else if (p.big8 && gemm8_supports(g.act, g.aux_kind, 256)) add(G8_256, 0, M, false);
+    else add(r224 ? T2_224 : T2_256, 0, M, false);
+    return p;
   }
-  const bool use_big = big && splitk_ws_floats > -2;  // -2 / -3: remainder rows of a split launch -> 128x128 / 64x128 tiles
-  const int BT = use_big ? 256 : 128;
-  // 224x256 tiles when they cover the problem in fewer (rounds x tile area) than 256x256 -- the N = 1536 GEMMs of the
-  // step: 38 x 6 = 228 tiles in one round instead of 204 tiles that are 14 % bigger
-  bool use_224 = false;
-  static const int no224 = FBL_ENV_INT("FBL_GEMM_NO224", 0);
-  if (use_big && splitk_ws_floats >= 0 && !no224) {
-    int dev = 0, n_cu = 256;
-    static int cu_cached = 0;
-    if (!cu_cached) {
-      hipDeviceProp_t prop;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cu_cached = prop.multiProcessorCount;
-      if (cu_cached <= 0) cu_cached = 256;
-    }
-    n_cu = cu_cached;
-    const long tn = (N + 255) / 256;
-    const long t256 = tn * ((M + 255) / 256), t224 = tn * ((M + 223) / 224);
-    const long c256 = ((t256 + n_cu - 1) / n_cu) * 256, c224 = ((t224 + n_cu - 1) / n_cu) * 224;
-    use_224 = c224 * 100 < c256 * 97;
-  }
-  // 64x128 tiles for tall, narrow problems whose 128x128 grid covers less than the chip (the adapter bottleneck
-  // projections: 8512 x 192 -> 134 workgroups): twice the workgroups, so twice the CUs pull operands from L2
-  static const int no64 = FBL_ENV_INT("FBL_GEMM_NO64", 0);
-  const bool use_64 = !use_big && !accumulate && !no64 && batch == 1 &&
-                      ((M >= 2048 && splitk_ws_floats >= 0) || splitk_ws_floats == -3) &&
-                      (long)((M + 127) / 128) * ((N + 127) / 128) < 200;
-  g.tiles_m = use_224 ? (M + 223) / 224 : use_64 ? (M + 63) / 64 : (M + BT - 1) / BT;
-  g.tiles_n = (N + BT - 1) / BT;
-  dim3 grid(g.tiles_m * g.tiles_n, batch * splitk);
-  // The 8-phase kernel (gemm8.hip) takes every launch of the 256- / 224-row configurations it is instantiated for.
-  // FBL_GEMM8=0 switches it off, 1 keeps the 224x256 shapes on the 2-stage kernel, 2 runs them as 256x256 8-phase tiles
-  // (measured: [8512,1536,6144] 915 -> 1139 TFLOP/s although only 204 of 256 CUs get a tile), 3 (default) as 224x256
-  // 8-phase tiles (228 tiles).
-  static const int gemm8_mode = FBL_ENV_INT("FBL_GEMM8", 3);
-  if (use_big && gemm8_mode > 0 && (!use_224 || gemm8_mode >= 2) && gemm8_eligible(g)) {
-    GemmArgs g8 = g;
-    const bool r224 = use_224 && gemm8_mode >= 3;
-    for (int attempt = r224 ? 0 : 1; attempt < 2; ++attempt) {  // 224-row tiles first where they apply, then 256-row tiles
-      const int bm = attempt == 0 ? 224 : 256;
-      g8.tiles_m = (M + bm - 1) / bm;
-      g8.tiles_n = (N + 255) / 256;
-      const int rc8 = launch_gemm8(g8, act, aux_kind, bm, dim3(g8.tiles_m * g8.tiles_n, 1), (hipStream_t)stream);
-      if (rc8 != FBL_ERR_ARG) return rc8;
-    }
-  }
+
+  const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
   // 128-row 8-phase tiles for problems the tall tiles leave half the chip idle on (the N = 1536 dX GEMMs at the row counts
   // of packed ragged batches / small batches: M = 5322 -> 21 x 6 = 126 tiles of 256 rows, 42 x 6 = 252 of 128 rows) and
   // that would otherwise run on the 128x128 two-stage kernel.  Chosen by a two-line cost model from measured per-K-tile
-  // times (tools/bench_gemm.py --set packed): rounds x (K-tiles x us per K-tile + epilogue).  FBL_GEMM_R128 (measurement
-  // builds): 0 = never, 2 = whenever the kernel can take the launch.
-  static const int r128_mode = FBL_ENV_INT("FBL_GEMM_R128", 1);
-  if (!use_big && r128_mode > 0 && gemm8_mode > 0 && !accumulate && batch == 1 && splitk_ws_floats >= 0 && !tail && seg_n <= 0 &&
-      p_drop <= 0.f && M >= 1024 && N >= 1024 && N <= 8192 && gemm8_eligible(g)) {
-    const int n_cu = device_cu_count();
-    const long t128 = (long)((M + 127) / 128) * ((N + 255) / 256), tsm = (long)((M + 127) / 128) * ((N + 127) / 128);
-    const double nk = K / 64.0;
-    const double us128 = (double)((t128 + n_cu - 1) / n_cu) * (nk * FBL_R128_US_PER_KTILE + 6.0);
-    const double ussm = (double)((tsm + 2 * n_cu - 1) / (2 * n_cu)) * (nk * 1.17 + 5.0);
-    if (r128_mode >= 2 || us128 < 0.95 * ussm) {
-      GemmArgs g8 = g;
-      g8.tiles_m = (M + 127) / 128;
-      g8.tiles_n = (N + 255) / 256;
-      const int rc8 = launch_gemm8(g8, act, aux_kind, 128, dim3(g8.tiles_m * g8.tiles_n, 1), (hipStream_t)stream);
-      if (rc8 != FBL_ERR_ARG) return rc8;
+  // times (tools/bench_gemm.py --set packed): rounds x (K-tiles x us per K-tile + epilogue).
+  if (!c.accumulate && c.batch == 1 && !tail && g.seg_n <= 0 && !c.dropout && M >= 1024 && N >= 1024 && N <= 8192 &&
+      gemm8_eligible(g) && gemm8_supports(g.act, g.aux_kind, 128)) {
+    const long t8 = (long)((M + 127) / 128) * ((N + 255) / 256);
+    const double us8 = (double)((t8 + n_cu - 1) / n_cu) * (nk * FBL_R128_US_PER_KTILE + 6.0);
+    const double us2 = (double)((t128 + 2 * n_cu - 1) / (2 * n_cu)) * (nk * 1.17 + 5.0);
+    if (us8 < 0.95 * us2) {
+      add(G8_128, 0, M, false);
+      return p;
     }
-  }
-#define FBL_GEMM_LAUNCH_NW(NW_, ACT_, AUX_, SK_, MI_)                                                           \
-  do {                                                                                                         \
-    static bool attr_set = false;                                                                              \
-    auto kfn = gemm_bf16_nt_kernel<NW_, ACT_, AUX_, SK_, 0, MI_>;                                              \
-    constexpr int smem_bytes = TileCfg<NW_>::SMEM_BYTES;                                                       \
-    if (!attr_set) {                                                                                           \
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes); \
-      if (e != hipSuccess) return (int)e;                                                                      \
-      attr_set = true;                                                                                         \
-    }                                                                                                          \
-    hipLaunchKernelGGL(kfn, grid, dim3(NW_ * 64), smem_bytes, (hipStream_t)stream, g);                         \
-  } while (0)
-  static const int deep64 = FBL_ENV_INT("FBL_GEMM_DEEP", 1);
-#define FBL_GEMM_LAUNCH_DEEP(ACT_, AUX_)                                                                        \
-  do {                                                                                                         \
-    static bool attr_set = false;                                                                              \
-    auto kfn = gemm_bf16_nt_kernel<4, ACT_, AUX_, false, 5, 2>;                                                \
-    constexpr int smem_bytes = 3 * (64 * BK * 2 + TileCfg<4>::TILE_BYTES);                                     \
-    static_assert(smem_bytes >= 4 * 64 * 68 * 4, "ring must cover the epilogue staging");                      \
-    if (!attr_set) {                                                                                           \
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes); \
-      if (e != hipSuccess) return (int)e;                                                                      \
-      attr_set = true;                                                                                         \
-    }                                                                                                          \
-    hipLaunchKernelGGL(kfn, grid, dim3(256), smem_bytes, (hipStream_t)stream, g);                              \
-  } while (0)
-#define FBL_GEMM_LAUNCH(ACT_, AUX_, SK_)                              \
-  do {                                                                \
-    if (use_224) FBL_GEMM_LAUNCH_NW(8, ACT_, AUX_, false, 7);         \
-    else if (use_big) FBL_GEMM_LAUNCH_NW(8, ACT_, AUX_, false, 8);    \
-    else if (use_64 && deep64) FBL_GEMM_LAUNCH_DEEP(ACT_, AUX_);      \
-    else if (use_64) FBL_GEMM_LAUNCH_NW(4, ACT_, AUX_, false, 2);     \
-    else FBL_GEMM_LAUNCH_NW(4, ACT_, AUX_, SK_, 4);                   \
-  } while (0)
-#define FBL_GEMM_LAUNCH_SCHED(SCHED_)                                                                          \
-  do {                                                                                                         \
-    static bool attr_set = false;                                                                              \
-    auto kfn = gemm_bf16_nt_kernel<8, FBL_ACT_NONE, FBL_AUX_NONE, false, SCHED_>;                              \
-    constexpr int smem_bytes = TileCfg<8>::SMEM_BYTES;                                                         \
-    if (!attr_set) {                                                                                           \
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes); \
-      if (e != hipSuccess) return (int)e;                                                                      \
-      attr_set = true;                                                                                         \
-    }                                                                                                          \
-    hipLaunchKernelGGL(kfn, grid, dim3(512), smem_bytes, (hipStream_t)stream, g);                              \
-  } while (0)
-  static const int exp_sched = FBL_ENV_INT("FBL_GEMM_SCHED", 0);
-  if (use_big && exp_sched > 0 && act == FBL_ACT_NONE && aux_kind == FBL_AUX_NONE) {  // experiment switch (plain epilogue)
-    if (exp_sched == 1) FBL_GEMM_LAUNCH_SCHED(1);
-    else if (exp_sched == 2) FBL_GEMM_LAUNCH_SCHED(2);
-    else if (exp_sched == 3) FBL_GEMM_LAUNCH_SCHED(3);
-    else FBL_GEMM_LAUNCH_SCHED(4);
-    FBL_CHECK_LAUNCH();
-    return 0;
   }
   // Few rows against a very long K with a workspace at hand (the prediction head's backward dh = dlogits . E: [~700 x 1536 x
   // 128128]): 8-phase 256 x 256 tiles, K cut into as many slices as fill the chip (18 tiles x 14 slices), partial tiles folded by
-  // splitk_reduce_kernel as below -- 463 -> ~235 us.  FBL_GEMM8_SK (measurement builds): 0 = the 128 x 128 two-stage kernel.
-  static const int sk8_on = FBL_ENV_INT("FBL_GEMM8_SK", 1);
-  bool done = false;
-  if (accumulate && sk8_on && g.ws && batch == 1 && M >= 512 && N >= 1024 && (K / BK) % 2 == 0 &&
-      K / BK >= 128 && (long)M * lda * 2 < (1l << 32) && (long)N * ldb * 2 < (1l << 32)) {
-    const int nk = K / BK, tiles = ((M + 255) / 256) * ((N + 255) / 256), n_cu = device_cu_count();
+  // splitk_reduce_kernel -- 463 -> ~235 us.
+  if (c.accumulate && g.ws && c.batch == 1 && M >= 512 && N >= 1024 && nk % 2 == 0 && nk >= 128 &&
+      (long)M * g.lda * 2 < (1l << 32) && (long)N * g.ldb * 2 < (1l << 32)) {
+    const int tiles = ((M + 255) / 256) * ((N + 255) / 256);
     int want = n_cu / tiles;
     if (want >= 2) {
       if (want > nk / 8) want = nk / 8;
@@ -661,53 +481,189 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, 
         per += 2;
         s8 = (nk + per - 1) / per;
       }
-      if (s8 >= 2 && per >= 8 && nk - (s8 - 1) * per >= 4 && (int64_t)s8 * M * Nw <= splitk_ws_floats) {
-        GemmArgs g8 = g;
-        g8.splitk = s8;
-        g8.k8_per = per;
-        g8.tiles_m = (M + 255) / 256;
-        g8.tiles_n = (N + 255) / 256;
-        const int rc8 = launch_gemm8_splitk(g8, (hipStream_t)stream);
-        if (rc8) return rc8;
-        splitk = s8;
-        done = true;
+      if (s8 >= 2 && per >= 8 && nk - (s8 - 1) * per >= 4 && (int64_t)s8 * M * g.Nw <= c.ws_floats) {
+        p.splitk = s8;
+        p.k8_per = per;
+        add(G8_SPLITK, 0, M, false);
+        return p;
       }
     }
   }
-  if (done) {
-  } else if (accumulate) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_NONE, true);
-  else if (act == FBL_ACT_GELU && aux_kind == FBL_AUX_NONE) FBL_GEMM_LAUNCH(FBL_ACT_GELU, FBL_AUX_NONE, false);
-  else if (act == FBL_ACT_RELU && aux_kind == FBL_AUX_NONE) FBL_GEMM_LAUNCH(FBL_ACT_RELU, FBL_AUX_NONE, false);
-  else if (act == FBL_ACT_GELU_GRAD && aux_kind == FBL_AUX_NONE) FBL_GEMM_LAUNCH(FBL_ACT_GELU_GRAD, FBL_AUX_NONE, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_MUL_BF16) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_MUL_BF16, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_NONE) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_NONE, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_ADD_F32) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_ADD_F32, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_ADD_BF16) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_ADD_BF16, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_MUL_DGELU_BF16) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_MUL_DGELU_BF16, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_MUL_POS_BF16) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_MUL_POS_BF16, false);
-  else if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_ADAPTER_TAIL) FBL_GEMM_LAUNCH(FBL_ACT_NONE, FBL_AUX_ADAPTER_TAIL, false);
-  else return FBL_ERR_ARG;
-#undef FBL_GEMM_LAUNCH
-#undef FBL_GEMM_LAUNCH_NW
-  FBL_CHECK_LAUNCH();
-  if (accumulate && g.ws) {
-    const long nq = (long)M * (Nw >> 2);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nq + 255) / 256), batch), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)g.ws, splitk, M, N, Nw, out_f32, (long)ldc, (long)strideC);
+  if (c.accumulate) {
+    add(T2_128_SPLITK, 0, M, false);
+  } else {
+    // 64x128 tiles for tall, narrow problems whose 128x128 grid covers less than the chip (the adapter bottleneck
+    // projections: 8512 x 192 -> 134 workgroups): twice the workgroups, so twice the CUs pull operands from L2
+    add(c.batch == 1 && M >= 2048 && t128 < 200 ? T2_64_RING : T2_128, 0, M, false);
   }
+  return p;
+}
+
+template <int NW, int ACT, int AUX, bool SPLITK, bool RING, int MI>
+static int launch_nt(const GemmArgs& g, dim3 grid, hipStream_t stream) {
+  constexpr int smem_bytes = RING ? 3 * (32 * MI * BK * 2 + TileCfg<NW>::TILE_BYTES) : TileCfg<NW>::SMEM_BYTES;
+  static_assert(smem_bytes >= NW * 64 * 68 * 4, "the LDS must cover the epilogue staging");
+  static bool attr_set = false;
+  auto kfn = gemm_bf16_nt_kernel<NW, ACT, AUX, SPLITK, RING, MI>;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(kfn, grid, dim3(NW * 64), smem_bytes, stream, g);
   FBL_CHECK_LAUNCH();
   return 0;
 }
 
-// Host-side query (no launch): which kernel fbl_gemm_bf16_nt gives a plain launch of this shape to -- 8: the 8-phase
-// kernel of gemm8.hip (whole rounds; a remainder of rows may go to 64x128 tiles of the 2-stage kernel), 2: the 2-stage kernel.
-extern "C" int fbl_gemm_plan(int M, int N, int K, int batch, int splitk) {
-  static const int force_small = FBL_ENV_INT("FBL_GEMM_SMALL", 0);
-  static const int gemm8_on = FBL_ENV_INT("FBL_GEMM8", 3);
-  if (force_small || gemm8_on <= 0 || splitk > 1 || !big_tile_shape(M, N, batch)) return 2;
+template <int ACT, int AUX>
+static int launch_two_stage(GemmKernel k, const GemmArgs& g, dim3 grid, hipStream_t stream) {
+  switch (k) {
+    case T2_256: return launch_nt<8, ACT, AUX, false, false, 8>(g, grid, stream);
+    case T2_224: return launch_nt<8, ACT, AUX, false, false, 7>(g, grid, stream);
+    case T2_64_RING: return launch_nt<4, ACT, AUX, false, true, 2>(g, grid, stream);
+    default: return launch_nt<4, ACT, AUX, false, false, 4>(g, grid, stream);
+  }
+}
+
+static int launch_one(const GemmLaunch& l, const GemmArgs& g, hipStream_t stream) {
+  const int act = g.act, aux = g.aux_kind;
+  switch (l.kernel) {
+    case G8_256: return launch_gemm8(g, act, aux, 256, l.grid, stream);
+    case G8_224: return launch_gemm8(g, act, aux, 224, l.grid, stream);
+    case G8_128: return launch_gemm8(g, act, aux, 128, l.grid, stream);
+    case G8_SPLITK: return launch_gemm8_splitk(g, stream);
+    case T2_128_SPLITK: return launch_nt<4, FBL_ACT_NONE, FBL_AUX_NONE, true, false, 4>(g, l.grid, stream);
+    default: break;
+  }
+  const GemmKernel k = l.kernel;
+  if (act == FBL_ACT_GELU && aux == FBL_AUX_NONE) return launch_two_stage<FBL_ACT_GELU, FBL_AUX_NONE>(k, g, l.grid, stream);
+  if (act == FBL_ACT_RELU && aux == FBL_AUX_NONE) return launch_two_stage<FBL_ACT_RELU, FBL_AUX_NONE>(k, g, l.grid, stream);
+  if (act == FBL_ACT_GELU_GRAD && aux == FBL_AUX_NONE) return launch_two_stage<FBL_ACT_GELU_GRAD, FBL_AUX_NONE>(k, g, l.grid, stream);
+  if (act != FBL_ACT_NONE) return FBL_ERR_ARG;
+  switch (aux) {
+    case FBL_AUX_NONE: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_NONE>(k, g, l.grid, stream);
+    case FBL_AUX_MUL_BF16: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_MUL_BF16>(k, g, l.grid, stream);
+    case FBL_AUX_ADD_F32: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_ADD_F32>(k, g, l.grid, stream);
+    case FBL_AUX_ADD_BF16: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_ADD_BF16>(k, g, l.grid, stream);
+    case FBL_AUX_MUL_DGELU_BF16: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_MUL_DGELU_BF16>(k, g, l.grid, stream);
+    case FBL_AUX_MUL_POS_BF16: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_MUL_POS_BF16>(k, g, l.grid, stream);
+    case FBL_AUX_ADAPTER_TAIL: return launch_two_stage<FBL_ACT_NONE, FBL_AUX_ADAPTER_TAIL>(k, g, l.grid, stream);
+    default: return FBL_ERR_ARG;
+  }
+}
+
+// The arguments of one launch of the plan: rows [row0, row0 + rows) of every row-indexed operand, dropout keys of the global
+// rows.  (The adapter tail, whose residual operands are row-indexed too, is never split.)
+static GemmArgs launch_args(GemmArgs g, const GemmPlan& p, const GemmLaunch& l) {
+  const long r0 = l.row0;
+  g.A += r0 * g.lda;
+  if (g.rowscale) g.rowscale += r0;
+  if (g.aux) g.aux = (const char*)g.aux + r0 * g.ld_aux * (g.aux_kind == FBL_AUX_ADD_F32 ? 4 : 2);
+  if (g.out_f32) g.out_f32 += r0 * g.ldc;
+  if (g.out_bf16) g.out_bf16 += r0 * g.ldc;
+  if (g.out_pre) g.out_pre += r0 * g.ldc;
+  if (g.seg_out) g.seg_out += r0 * g.seg_ld;
+  g.drop_row0 += r0;
+  g.M = l.rows;
+  g.splitk = p.splitk;
+  g.k8_per = p.k8_per;
+  g.tiles_m = l.tiles_m;
+  g.tiles_n = l.tiles_n;
+  return g;
+}
+
+static int run_plan(const GemmPlan& p, const GemmArgs& g, int batch, hipStream_t stream, hipStream_t aux_stream) {
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  for (int i = 0; i < p.n; ++i) {
+    const GemmLaunch& l = p.launch[i];
+    hipStream_t s = stream;
+    if (l.on_aux) {
+      if (!fork_join_events(stream, aux_stream, &ev_fork, &ev_join)) return FBL_ERR_ARG;
+      if (hipEventRecord(ev_fork, stream) != hipSuccess) return FBL_ERR_ARG;
+      if (hipStreamWaitEvent(aux_stream, ev_fork, 0) != hipSuccess) return FBL_ERR_ARG;
+      s = aux_stream;
+    }
+    if (const int rc = launch_one(l, launch_args(g, p, l), s)) return rc;
+    if (l.on_aux && hipEventRecord(ev_join, aux_stream) != hipSuccess) return FBL_ERR_ARG;
+  }
+  if (ev_join && hipStreamWaitEvent(stream, ev_join, 0) != hipSuccess) return FBL_ERR_ARG;
+  if (p.fold) {
+    const long nq = (long)g.M * (g.Nw >> 2);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nq + 255) / 256), batch), dim3(256), 0, stream,
+                       (const float*)g.ws, p.splitk, g.M, g.N, g.Nw, g.out_f32, g.ldc, g.sC);
+    FBL_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+// GemmArgs of C[M,N] = A[M,K] . B[N,K]^T with every option off; the entry points fill in theirs
+static GemmArgs nt_args(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K) {
   GemmArgs g{};
-  g.M = M; g.N = N; g.K = K; g.lda = K; g.ldb = K; g.splitk = 1;
-  return gemm8_eligible(g) ? 8 : 2;
+  g.A = (const bf16*)A; g.B = (const bf16*)B; g.lda = lda; g.ldb = ldb;
+  g.M = M; g.N = N; g.K = K;
+  g.alpha = 1.f; g.act = FBL_ACT_NONE; g.aux_kind = FBL_AUX_NONE;
+  g.splitk = 1; g.drop_inv_keep = 1.f;
+  return g;
+}
+
+// Validates a call, completes its GemmArgs (split-K, dropout, keys of the tail / segment outputs) and runs its plan.
+// splitk >= 2 asks for C += A.B^T (atomically, or through splitk_ws when that holds batch*splitk*M*roundup(N,4) floats).
+// p_drop > 0 (ReLU epilogue, the second segment or the adapter tail): dropout of the activated output, element (m, n) keyed by
+// (drop_seed, m*ldc + n).
+static int gemm_nt(GemmArgs g, int batch, int splitk, float* splitk_ws, int64_t splitk_ws_floats, float p_drop, void* stream,
+                   void* aux_stream) {
+  const int M = g.M, N = g.N, K = g.K;
+  const bool tail = g.aux_kind == FBL_AUX_ADAPTER_TAIL;
+  if (M <= 0 || N <= 0 || batch <= 0) return 0;
+  if (K <= 0 || (K % BK) != 0) return FBL_ERR_SHAPE;               // K must be a multiple of 64 (callers zero-pad)
+  if ((g.lda % 8) != 0 || (g.ldb % 8) != 0) return FBL_ERR_ALIGN;  // 16-byte operand rows
+  if (splitk < 1) splitk = 1;
+  const bool accumulate = splitk > 1;  // callers ask for splitk >= 2 when they want "out += A.B^T"
+  if (splitk > 1) {  // every split must own at least one K tile
+    const int nk = K / BK;
+    const int per = (nk + splitk - 1) / splitk;
+    splitk = (nk + per - 1) / per;
+  }
+  g.splitk = splitk;
+  g.Nw = (N + 3) & ~3;
+  if (accumulate && splitk_ws && (int64_t)batch * splitk * M * g.Nw <= splitk_ws_floats) g.ws = splitk_ws;  // (too small: unused)
+  if (accumulate && g.bias && g.ws) return FBL_ERR_ARG;
+  if (accumulate && (!g.out_f32 || g.out_bf16 || g.out_pre || g.act != FBL_ACT_NONE || g.aux_kind != FBL_AUX_NONE))
+    return FBL_ERR_ARG;  // split-K only accumulates (atomicAdd) into a pre-initialised fp32 output
+  if (!g.out_f32 && !g.out_bf16) return FBL_ERR_ARG;
+  g.drop_ld = g.ldc;
+  if (tail) {
+    if (accumulate || batch != 1 || g.seg_n > 0 || !g.out_f32 || g.out_bf16 || g.out_pre || g.act != FBL_ACT_NONE ||
+        g.rowscale || !g.aux || !g.r_t || (N & 3) || (g.ldc & 3) || (g.ld_aux & 3) || (g.ld_r & 3) ||
+        (g.r_stats && (!g.r_gamma || !g.r_beta)))
+      return FBL_ERR_ARG;
+    g.drop_ld = N;  // keys of fbl_ln_fwd: (seed, m*H + n)
+  }
+  if (g.seg_n > 0) {
+    // The epilogue branches per LANE on "column >= seg_n" but stages accumulators through per-WAVE LDS patches that all 64
+    // lanes fill: the segment boundary must not cut a wave's column range.  A wave of the 2-stage kernels owns 64
+    // contiguous columns, a wave of the 256-wide tiles (2-stage and 8-phase) two 32-column ranges 128 apart -> the
+    // boundary has to be a multiple of 64, and of 256 for the wide tiles (otherwise the narrow tiles take the problem).
+    if ((g.seg_n & 63) || g.seg_n >= N || !g.seg_out || accumulate || batch != 1) return FBL_ERR_ARG;
+    g.drop_ld = g.seg_ld;
+  }
+  if (p_drop > 0.f) {
+    if ((g.act != FBL_ACT_RELU && g.seg_n <= 0 && !tail) || p_drop >= 1.f || batch != 1) return FBL_ERR_ARG;
+    g.drop_thresh = fbl_drop_thresh(p_drop);
+    g.drop_inv_keep = 1.f / (1.f - p_drop);
+  }
+  const GemmCall c{batch, accumulate, p_drop > 0.f, splitk_ws != nullptr, splitk_ws_floats,
+                   aux_stream != nullptr && aux_stream != stream, device_cu_count()};
+  return run_plan(plan_gemm(g, c), g, batch, (hipStream_t)stream, (hipStream_t)aux_stream);
+}
+
+// Host-side query (no launch, no HIP call): whether fbl_gemm_bf16_nt gives a plain launch of this shape to the big-tile route
+// of the 8-phase kernel -- 8: 256- / 224-row tiles of gemm8.hip (a remainder of rows may go to small tiles of the 2-stage
+// kernel), 2: otherwise (the 2-stage kernel, or the 128-row 8-phase tiles of a problem too short for the big ones).  That
+// decision does not depend on the CU count; the planner is given the MI355X's 256.
+extern "C" int fbl_gemm_plan(int M, int N, int K, int batch, int splitk) {
+  const GemmCall c{batch, splitk > 1, false, false, 0, false, 256};
+  return plan_gemm(nt_args(nullptr, K, nullptr, K, M, N, K), c).big8 ? 8 : 2;
 }
 
 extern "C" int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
@@ -717,9 +673,11 @@ extern "C" int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64
                                 int64_t strideAux, int64_t strideBias, int splitk, float* splitk_ws,
                                 int64_t splitk_ws_floats, void* stream, void* aux_stream) {
   if (aux_kind == FBL_AUX_ADAPTER_TAIL) return FBL_ERR_ARG;  // (has its own entry point: fbl_adapter_up_resid_fwd)
-  return gemm_nt_impl(A, lda, B, ldb, M, N, K, bias, rowscale, alpha, act, aux_kind, aux, ld_aux, out_f32, out_bf16,
-                      out_pre_bf16, ldc, batch, strideA, strideB, strideC, strideAux, strideBias, splitk, splitk_ws,
-                      splitk_ws_floats, 0.f, 0, stream, 0, nullptr, 0, 0, aux_stream);
+  GemmArgs g = nt_args(A, lda, B, ldb, M, N, K);
+  g.bias = bias; g.rowscale = rowscale; g.alpha = alpha; g.act = act; g.aux_kind = aux_kind; g.aux = aux; g.ld_aux = ld_aux;
+  g.out_f32 = out_f32; g.out_bf16 = (bf16*)out_bf16; g.out_pre = (bf16*)out_pre_bf16; g.ldc = ldc;
+  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sAux = strideAux; g.sBias = strideBias;
+  return gemm_nt(g, batch, splitk, splitk_ws, splitk_ws_floats, 0.f, stream, aux_stream);
 }
 
 // z[M, A] = dropout(relu(x[M,K] . Wd[A,K]^T + bd)): the adapter's down-projection with ReLU AND dropout in the GEMM
@@ -727,9 +685,10 @@ extern "C" int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64
 extern "C" int fbl_adapter_down_fwd(const void* x_bf16, int64_t ldx, const void* wd_bf16, int64_t ldw, int M, int A, int K,
                                     const float* bias, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* z_bf16,
                                     int64_t ldz, void* stream) {
-  return gemm_nt_impl(x_bf16, ldx, wd_bf16, ldw, M, A, K, bias, nullptr, 1.0f, FBL_ACT_RELU, FBL_AUX_NONE, nullptr, 0,
-                      nullptr, z_bf16, nullptr, ldz, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, p_drop, seed, stream, 0,
-                      nullptr, 0, 0, nullptr, nullptr, seed_dev);
+  GemmArgs g = nt_args(x_bf16, ldx, wd_bf16, ldw, M, A, K);
+  g.bias = bias; g.act = FBL_ACT_RELU; g.out_bf16 = (bf16*)z_bf16; g.ldc = ldz;
+  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  return gemm_nt(g, 1, 1, nullptr, 0, p_drop, stream, nullptr);
 }
 
 // One GEMM for a dense layer AND the down-projection of the adapter that follows it (model/deberta.py:255-257, 329-331:
@@ -744,9 +703,11 @@ extern "C" int fbl_dense_adapter_down_fwd(const void* x_bf16, int64_t ldx, const
                                           float p_drop, uint64_t seed, const uint64_t* seed_dev, void* z_bf16, int64_t ldz,
                                           void* stream, void* aux_stream) {
   if (A <= 0 || (N1 & 63)) return FBL_ERR_ARG;
-  return gemm_nt_impl(x_bf16, ldx, wm_bf16, ldw, M, N1 + A, K, bias_m, nullptr, 1.0f, FBL_ACT_NONE, FBL_AUX_NONE, nullptr, 0,
-                      y_f32, y_bf16, nullptr, ldy, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, p_drop, seed, stream, N1,
-                      z_bf16, ldz, 0, aux_stream, nullptr, seed_dev);
+  GemmArgs g = nt_args(x_bf16, ldx, wm_bf16, ldw, M, N1 + A, K);
+  g.bias = bias_m; g.out_f32 = y_f32; g.out_bf16 = (bf16*)y_bf16; g.ldc = ldy;
+  g.seg_n = N1; g.seg_out = (bf16*)z_bf16; g.seg_ld = ldz;
+  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  return gemm_nt(g, 1, 1, nullptr, 0, p_drop, stream, aux_stream);
 }
 
 extern "C" int fbl_adapter_up_resid_fwd(const void* z_bf16, int64_t ldz, const void* wu_bf16, int64_t ldw, int M, int H, int A,
@@ -757,10 +718,11 @@ extern "C" int fbl_adapter_up_resid_fwd(const void* z_bf16, int64_t ldz, const v
   if (!z_bf16 || !wu_bf16 || !x_bf16 || !r_t || !out_t) return FBL_ERR_ARG;
   if (p_drop < 0.f || p_drop >= 1.f) return FBL_ERR_ARG;
   if (ldx % 8) return FBL_ERR_ALIGN;
-  const TailArgs tail{r_t, ld_r, r_stats, r_gamma, r_beta, r_rowmask};
-  return gemm_nt_impl(z_bf16, ldz, wu_bf16, ldw, M, H, A, bias_u, nullptr, 1.0f, FBL_ACT_NONE, FBL_AUX_ADAPTER_TAIL, x_bf16, ldx,
-                      out_t, nullptr, nullptr, ldt, 1, 0, 0, 0, 0, 0, 1, nullptr, 0, p_drop, seed, stream, 0,
-                      nullptr, 0, 0, nullptr, &tail, seed_dev);
+  GemmArgs g = nt_args(z_bf16, ldz, wu_bf16, ldw, M, H, A);
+  g.bias = bias_u; g.aux_kind = FBL_AUX_ADAPTER_TAIL; g.aux = x_bf16; g.ld_aux = ldx; g.out_f32 = out_t; g.ldc = ldt;
+  g.r_t = r_t; g.ld_r = ld_r; g.r_stats = r_stats; g.r_gamma = r_gamma; g.r_beta = r_beta; g.r_rowmask = r_rowmask;
+  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  return gemm_nt(g, 1, 1, nullptr, 0, p_drop, stream, nullptr);
 }
 
 extern "C" int fbl_gemm_bf16_tn_acc(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,

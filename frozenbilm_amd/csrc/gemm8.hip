@@ -326,7 +326,15 @@ bool gemm8_eligible(const GemmArgs& g) {
   return true;
 }
 
-// rows: 256, 224 or 128 (tile height)
+// The epilogues instantiated at each tile height (rows: 256, 224 or 128) -- launch_gemm8 below takes exactly these
+bool gemm8_supports(int act, int aux_kind, int rows) {
+  if (act == FBL_ACT_NONE && (aux_kind == FBL_AUX_NONE || aux_kind == FBL_AUX_ADD_F32)) return rows == 256 || rows == 224 || rows == 128;
+  if (rows != 256) return false;
+  if (aux_kind == FBL_AUX_NONE) return act == FBL_ACT_GELU || act == FBL_ACT_GELU_GRAD;
+  return act == FBL_ACT_NONE &&
+         (aux_kind == FBL_AUX_ADD_BF16 || aux_kind == FBL_AUX_MUL_BF16 || aux_kind == FBL_AUX_MUL_DGELU_BF16);
+}
+
 int launch_gemm8(const GemmArgs& g, int act, int aux_kind, int rows, dim3 grid, hipStream_t stream) {
   if (rows == 224) {  // the N = 1536 GEMMs of the step: plain (one or two outputs) and residual-add epilogues
     if (act == FBL_ACT_NONE && aux_kind == FBL_AUX_NONE) return launch_variant<FBL_ACT_NONE, FBL_AUX_NONE, 1>(g, grid, stream);

@@ -440,10 +440,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, char* smem, int
   if constexpr ((MI + 3) / 4 > 1) slab(std::integral_constant<int, 1>{});
 }
 
-// 8-phase 256x256 kernel (gemm8.hip).  Returns 0 when launched, FBL_ERR_ARG for an epilogue combination it does not
-// instantiate (the caller then uses the 2-stage kernel).
-int launch_gemm8(const GemmArgs& g, int act, int aux_kind, int rows, dim3 grid, hipStream_t stream);  // rows: 256 / 224 / 128
+// 8-phase kernel (gemm8.hip).  gemm8_eligible: the shape and options it can run; gemm8_supports: whether it instantiates the
+// epilogue (act, aux_kind) at tile height rows (256 / 224 / 128).  launch_gemm8 takes only supported combinations
+// (FBL_ERR_ARG otherwise).
+int launch_gemm8(const GemmArgs& g, int act, int aux_kind, int rows, dim3 grid, hipStream_t stream);
 bool gemm8_eligible(const GemmArgs& g);
+bool gemm8_supports(int act, int aux_kind, int rows);
 int launch_gemm8_splitk(const GemmArgs& g, hipStream_t stream);  // plain 256-row tiles, g.splitk slices of g.k8_per K-tiles -> g.ws
 
 

@@ -70,9 +70,10 @@ int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, int
                      int64_t strideB, int64_t strideC, int64_t strideAux, int64_t strideBias, int splitk,
                      float* splitk_ws, int64_t splitk_ws_floats, void* stream, void* aux_stream);
 
-/* Host-side query, no launch: the kernel fbl_gemm_bf16_nt uses for a plain problem of this
- * shape: 8 = the 8-phase 256x256 / 224x256 kernel (gemm8_kernel; remainder rows of a multi-round problem run as 64x128
- * tiles), 2 = the 2-stage 128x128 / 64x128 kernel.  bench.py attributes launches to the dominant kernel with it. */
+/* Host-side query, no launch, no HIP call: the big-tile route of fbl_gemm_bf16_nt for a plain problem of this shape.
+ * 8 = big tiles on the 8-phase kernel (gemm8_kernel, 256x256 / 224x256; remainder rows of a multi-round problem run on
+ * small tiles of the 2-stage kernel), 2 = otherwise (the 2-stage kernel, or 128-row 8-phase tiles for a problem too short
+ * for the big ones).  bench.py attributes launches to the dominant kernel with it. */
 int fbl_gemm_plan(int M, int N, int K, int batch, int splitk);
 
 /* Adapter down-projection with the whole bottleneck non-linearity in the GEMM epilogue:

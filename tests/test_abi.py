@@ -51,7 +51,7 @@ def test_library_exports_every_symbol(libpath):
 
 
 def test_product_library_reads_no_environment(libpath):
-    """The experiment switches (FBL_GEMM_*, FBL_ATTN_*) exist only in FBL_DEBUG_BUILD=1 builds: the product library
+    """The experiment switches (FBL_GEMM8_VAR, FBL_ATTN_*) exist only in FBL_DEBUG_BUILD=1 builds: the product library
     does not even import getenv, and owns no stream (no hipStreamCreate*: helper streams are caller-provided)."""
     import subprocess
 

@@ -1,8 +1,7 @@
 """Micro-benchmark (+ optional correctness check) of fbl_gemm_bf16_nt on the hot-path shapes, HIP events on the launch stream.
 usage: python tools/bench_gemm.py [--iters 20] [--check] [--set hot|square|all]
-Kernel selection switches are environment variables read once per process (FBL_GEMM8, FBL_GEMM8_VAR, FBL_GEMM_NO224, ...),
-so A/B comparisons run this script once per setting.  Operands are uniform random in [-1, 1) (never zero-filled: the chip
-clocks higher on zeros).  --check compares against an fp32 torch matmul of the same bf16 operands (tool only)."""
+Operands are uniform random in [-1, 1) (never zero-filled: the chip clocks higher on zeros).
+--check compares against an fp32 torch matmul of the same bf16 operands (tool only)."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,6 +1,5 @@
 """HIP-event timing of the adapter tail (fbl_adapter_up_resid_fwd: up-projection + dropout + residual -> pre-norm tensor) and of
-the LayerNorm statistics pass behind it at the bench shape; with the debug library FBL_GEMM_SMALL=1 runs the GEMM on 128x128
-tiles (two workgroups per CU) instead of the 224x256 ones."""
+the LayerNorm statistics pass behind it at the bench shape."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
