@@ -38,13 +38,15 @@ def _relidx_range(S, cfg):
 
 
 _DRANGE = {}
-POS_GRAD_MAX_DELTAS = 8  # deltas per table row fbl_attn_pos_grad takes (dcnt_max)
+POS_GRAD_MAX_DELTAS = 8  # deltas per table row the walking kernel of fbl_attn_pos_grad takes (beyond: its prefix-difference kernel)
 
 
-def _delta_ranges(S, cfg, dev):
+def _delta_ranges(S, cfg, dev, limit=POS_GRAD_MAX_DELTAS):
     """(dlo, dcnt, max dcnt): int16 device tensors [rcnt]: table row rmin + r collects the deltas [dlo[r], dlo[r] + dcnt[r]) -- the inverse
-    of the (monotone) relative-index vector, computed once per sequence length.  Raises NotImplementedError for a bucket map that
-    puts more than POS_GRAD_MAX_DELTAS deltas on one table row (the FrozenBiLM map, 256 buckets / 512 positions, peaks at 6)."""
+    of the (monotone) relative-index vector, computed once per sequence length.  With a limit (default POS_GRAD_MAX_DELTAS: the
+    maps the walking kernel takes), raises NotImplementedError for a bucket map that puts more than `limit` deltas on one table
+    row (the FrozenBiLM map, 256 buckets / 512 positions, peaks at 6); limit=None takes every map -- fbl_attn_pos_grad picks
+    its kernel from the max, as the position-table gradients do."""
     key = (S, cfg.position_buckets, cfg.max_rel, cfg.att_span, str(dev))
     if key not in _DRANGE:
         import numpy as np
@@ -57,13 +59,13 @@ def _delta_ranges(S, cfg, dev):
         last = np.searchsorted(rv, np.arange(rmin, rmin + rcnt), side="right")
         dlo = (first - (S - 1)).astype(np.int16)
         dcnt = (last - first).astype(np.int16)
-        cmax = int(dcnt.max())
-        if cmax > POS_GRAD_MAX_DELTAS:
-            raise NotImplementedError(
-                f"position-table gradients (fbl_attn_pos_grad) take at most {POS_GRAD_MAX_DELTAS} relative positions per table "
-                f"row; position_buckets={cfg.position_buckets}, max_relative_positions={cfg.max_rel} at sequence length {S} "
-                f"puts {cmax} on one row")
-        _DRANGE[key] = (torch.from_numpy(dlo).to(dev), torch.from_numpy(dcnt).to(dev), cmax)
+        _DRANGE[key] = (torch.from_numpy(dlo).to(dev), torch.from_numpy(dcnt).to(dev), int(dcnt.max()))
+    cmax = _DRANGE[key][2]
+    if limit is not None and cmax > limit:
+        raise NotImplementedError(
+            f"position-table gradients (fbl_attn_pos_grad) take at most {limit} relative positions per table "
+            f"row; position_buckets={cfg.position_buckets}, max_relative_positions={cfg.max_rel} at sequence length {S} "
+            f"puts {cmax} on one row")
     return _DRANGE[key]
 
 
@@ -100,8 +102,10 @@ def disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk, defer_pos=False):
     L.attn_bwd_prep(q, pq, pk, dctx, sv.ctx, QT, PQT, Dv, B, S, Sp, nh, span2, row0=row0, relidx=relidx, PQX=PQX, PKX=PKX)
     dS = torch.empty(B, nh, Sp, Sp, dtype=BF16, device=dev)
     dST = torch.empty(B, nh, Sp, Sp, dtype=BF16, device=dev)
-    # |i-j| < lin: identity buckets, relidx injective (model/deberta.py:578-589: mid = bucket_size // 2)
-    lin = eng.cfg.position_buckets // 2 if eng.cfg.position_buckets > 0 else 1 << 30
+    # |i-j| < lin: relidx injective -- identity buckets (model/deberta.py:578-589: mid = bucket_size // 2), or a clamped table
+    # (position_buckets <= 0): clamp(delta + span, 0, 2 span - 1) puts delta = span - 1 AND every delta >= span on the top edge
+    # row (every delta <= -span on the bottom one), so it is injective for |delta| < span - 1
+    lin = eng.cfg.position_buckets // 2 if eng.cfg.position_buckets > 0 else eng.cfg.att_span - 1
     if saved_p:
         # kernel A from the probabilities the training forward saved, dK formed in place
         L.disent_attn_bwd_dspk(sv.psave, sv.msave, q, v, dctx, PQX, sv.lse, Dv, scale, dqkv[:, H:2 * H], dqkv[:, 2 * H:], dS, dST,
@@ -131,7 +135,7 @@ def pos_table_grads(eng, st):
     H, nh, span2 = eng.H, eng.nh, eng.span2
     rmin, rcnt, B, Sp = st["rmin"], st["rcnt"], st["B"], st["Sp"]
     dpos = torch.zeros(span2, 2 * H, dtype=F32, device=eng.dev)
-    dlo, dcnt, cmax = _delta_ranges(st["S"], eng.cfg, eng.dev)
+    dlo, dcnt, cmax = _delta_ranges(st["S"], eng.cfg, eng.dev, limit=None)
     for neg, X, Y, col0 in ((0, st["dS"], st["q"], H), (1, st["dST"], st["k"], 0)):
         d = torch.empty(1, nh, rcnt, 64, dtype=F32, device=eng.dev)
         L.attn_pos_grad(neg, [X], [Y], dlo, dcnt, cmax, d, B, st["S"], Sp, nh, rcnt, klen=st["klen"], row0=st["row0"])
@@ -165,7 +169,7 @@ def pos_table_grads_batched(eng, run, pc):
     # [dPQ | dPK] of every execution, rows rmin .. rmin + rcnt of the tables (the others cannot be touched: their gradient is
     # zero): bf16 operand of the projection, fully written by the two copies below
     dpb = torch.empty(E, rcnt, 2 * H, dtype=BF16, device=dev)
-    dlo, dcnt, cmax = _delta_ranges(pc["S"], eng.cfg, dev)
+    dlo, dcnt, cmax = _delta_ranges(pc["S"], eng.cfg, dev, limit=None)
     for neg, kx, ky, col0 in ((0, "X1", "Yq", H), (1, "X2", "Yk", 0)):
         d = torch.empty(E, nh, rcnt, 64, dtype=F32, device=dev)
         L.attn_pos_grad(neg, pc[kx][:E], pc[ky][:E], dlo, dcnt, cmax, d, B, pc["S"], Sp, nh, rcnt, klen=pc["klen"], row0=pc["row0"])

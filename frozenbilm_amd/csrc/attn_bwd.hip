@@ -1127,7 +1127,7 @@ __host__ __device__ constexpr int pg_buf(int Sp) { return 32 * pg_pitch(Sp) * 2 
 __host__ __device__ constexpr int pg_smem(int Sp) { return 2 * pg_buf(Sp); }
 
 // CM: upper bound of dcnt (deltas per table row): 3 or 8, chosen from dcnt_max by the launcher (the FrozenBiLM bucket map,
-// position_buckets 256 / max_relative_positions 512, peaks at 6 for S <= 512; maps beyond 8 are rejected)
+// position_buckets 256 / max_relative_positions 512, peaks at 6 for S <= 512; maps beyond 8 run pos_grad_wide_kernel)
 // NXR: 16-byte chunks of X per thread and block (Sp / 64); OCC: workgroups per CU the register budget is set for (3: one staging
 // buffer and two barriers per item, 2: two buffers and one barrier)
 template <bool NEG, int CM, int NXR, int OCC>
@@ -1286,6 +1286,158 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
   }
 }
 
+// Any bucket map (dcnt_max > 8: coarse log buckets, or the two edge rows of a clamped table that collect every delta beyond
+// the span, up to S - att_span of them).  For a staged row k the deltas of table row r reach ONE contiguous column range, so
+//   G[r][k] = C_k(jhi) - C_k(jlo),   C_k(j) = sum_{col < j} X[k][col]   (fp32; j clamped into [0, Sp])
+// with [jlo, jhi) = [k - d0 - dn + 1, k - d0 + 1) (NEG = 0) or [k + d0, k + d0 + dn) (NEG = 1): two LDS reads per element
+// whatever dn is.  The staging turns the 32 rows of X into their prefix sums (8 threads per row: a running sum over each
+// 8-column chunk, a 3-step scan across the 8 threads, the carry of the previous 64 columns).  Work split, work list, Y
+// staging, MFMAs and the batch sum in registers are those of pos_grad_kernel; one staging buffer (32 x (Sp + PGW_PAD) fp32
+// = 65 KB at Sp = 512) and two barriers per item, two workgroups per CU.  Deterministic: fixed summation order, no atomics.
+constexpr int PGW_PAD = 6;  // fp32 row pitch Sp + 6: C_k(j) at k * pitch + 1 + j, pairs (j odd, j + 1) 8-byte aligned; the 8
+                            // rows a lane group walks start 16 banks apart
+__host__ __device__ constexpr int pgw_pitch(int Sp) { return Sp + PGW_PAD; }
+__host__ __device__ constexpr int pgw_smem(int Sp) { return 32 * pgw_pitch(Sp) * 4 + 32 * PG_LDY * 2; }
+
+template <bool NEG>
+__global__ __launch_bounds__(PG_THR, 2) void pos_grad_wide_kernel(PosGradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 15, g = lane >> 4;
+  const int S = a.S, Sp = a.Sp, PP = pgw_pitch(Sp);
+  const int nsplit = (a.rcnt + PG_ROWS - 1) / PG_ROWS;
+  const int L8 = blockIdx.x >> 3, xcd = blockIdx.x & 7;
+  const int prob = (L8 / nsplit) * 8 + xcd, part = L8 % nsplit;
+  if (prob >= a.E * a.nh) return;
+  const int e = prob / a.nh, h = prob % a.nh;
+  float* cs = (float*)smem;                       // [32][PP] prefix sums of the staged rows of X
+  bf16* ys = (bf16*)(smem + 32 * PP * 4);         // [32][PG_LDY] rows of Y
+  const bf16* X = a.X[e];
+  const bf16* Y = a.Y[e];
+  const int ntiles = (a.rcnt + 15) / 16;
+
+  int d0[PG_TPW], dn[PG_TPW], tlo[PG_TPW], thi[PG_TPW];
+#pragma unroll
+  for (int u = 0; u < PG_TPW; ++u) {
+    const int t = (w + PG_WAVES * u) * nsplit + part;
+    const int r = min(t * 16 + c, a.rcnt - 1);
+    const bool live = t < ntiles && t * 16 + c < a.rcnt;
+    d0[u] = live ? (int)a.dlo[r] : 0;
+    dn[u] = live ? (int)a.dcnt[r] : 0;  // 0: jlo == jhi, G = 0
+    const int rf = min(t * 16, a.rcnt - 1), rl = min(t * 16 + 15, a.rcnt - 1);
+    tlo[u] = t < ntiles ? (int)a.dlo[rf] : 1 << 20;
+    thi[u] = t < ntiles ? (int)a.dlo[rl] + (int)a.dcnt[rl] - 1 : -(1 << 20);
+  }
+  f32x4 acc[PG_TPW][4];
+#pragma unroll
+  for (int u = 0; u < PG_TPW; ++u)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) acc[u][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  // C_k(0) = 0 is written once; the staging rewrites C_k(1 .. Sp)
+  if (tid < 32) cs[tid * PP + 1] = 0.f;
+  const bf16x8 z8 = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+  const int srow = tid >> 3, sch = tid & 7, nq = Sp >> 6;
+
+  int b_n = 0, k_n = 0, kl_n = 0;
+  auto seek = [&]() {
+    while (b_n < a.B) {
+      kl_n = a.klen ? min(a.klen[b_n], S) : S;
+      if (k_n < kl_n) return true;
+      ++b_n; k_n = 0;
+    }
+    return false;
+  };
+  bf16x8 rx[8], ry;
+  int it_k = 0, it_kl = 0;
+  auto load_item = [&]() {
+    it_k = k_n; it_kl = kl_n;
+    const int kl64 = (kl_n + 63) & ~63;
+    const long rb = a.row0 ? (long)a.row0[b_n] : (long)b_n * S;
+    const int lim = a.row0 ? min(a.row0[b_n + 1] - a.row0[b_n], S) : S;
+    const bf16* xr = X + (((long)b_n * a.nh + h) * Sp) * Sp + (long)(k_n + srow) * Sp + sch * 8;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) rx[q] = (q < nq && sch * 8 + q * 64 < kl64) ? *(const bf16x8*)(xr + q * 64) : z8;
+    const int pos = k_n + srow;
+    ry = (pos < lim) ? *(const bf16x8*)(Y + (rb + pos) * a.ldy + h * 64 + sch * 8) : z8;
+    k_n += 32;
+  };
+  bool have = seek();
+  if (have) load_item();
+  while (have) {
+    __syncthreads();  // the previous item's fragments are read
+    {
+      // chunk q of this thread: columns q*64 + sch*8 .. +7 of row srow; the 8 threads of a row are 8 consecutive lanes
+      float* cw = cs + srow * PP + 2 + sch * 8;  // C_k(col + 1)
+      float carry = 0.f;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if (q < nq) {
+          float run[8];
+          run[0] = bf2f(rx[q][0]);
+#pragma unroll
+          for (int i = 1; i < 8; ++i) run[i] = run[i - 1] + bf2f(rx[q][i]);
+          float incl = run[7];
+#pragma unroll
+          for (int s = 1; s < 8; s <<= 1) {
+            const float o = __shfl_up(incl, s, 8);
+            if (sch >= s) incl += o;
+          }
+          const float excl = __shfl_up(incl, 1, 8);
+          const float base = carry + (sch ? excl : 0.f);
+#pragma unroll
+          for (int i = 0; i < 8; i += 2) *(float2*)(cw + q * 64 + i) = make_float2(base + run[i], base + run[i + 1]);
+          carry += __shfl(incl, 7, 8);
+        }
+      }
+    }
+    *(bf16x8*)(ys + srow * PG_LDY + sch * 8) = ry;
+    const int k0 = it_k, kl = it_kl;
+    __syncthreads();
+    have = seek();
+    if (have) load_item();
+    bf16x8 yf[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      const bf16* yb = ys + (g * 8 + (c >> 2)) * PG_LDY + dt * 16 + (c & 3) * 4;
+      union { tr16x4 hh[2]; bf16x8 v; } u2;
+      u2.hh[0] = lds_tr16(yb);
+      u2.hh[1] = lds_tr16(yb + 4 * PG_LDY);
+      yf[dt] = u2.v;
+    }
+    const float* crow = cs + (g * 8) * PP + 1;  // C of staged row g*8 + q: crow[q * PP + j]
+#pragma unroll
+    for (int u = 0; u < PG_TPW; ++u) {
+      const int cmin = NEG ? k0 + tlo[u] : k0 - thi[u];
+      const int cmax = NEG ? k0 + 31 + thi[u] : k0 + 31 - tlo[u];
+      if (cmax < 0 || cmin >= kl) continue;  // (wave-uniform)
+      const int kb = k0 + g * 8;
+      float hi[8], lo[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int jl = NEG ? kb + q + d0[u] : kb + q - d0[u] - dn[u] + 1;
+        hi[q] = crow[q * PP + clampi(jl + dn[u], 0, Sp)];
+        lo[q] = crow[q * PP + clampi(jl, 0, Sp)];
+      }
+      bf16x8 gf;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) gf[q] = f2bf(hi[q] - lo[q]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) acc[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(yf[dt], gf, acc[u][dt], 0, 0, 0);
+    }
+  }
+  float* ob = a.out + ((long)e * a.nh + h) * a.rcnt * 64;
+#pragma unroll
+  for (int u = 0; u < PG_TPW; ++u) {
+    const int r = ((w + PG_WAVES * u) * nsplit + part) * 16 + c;
+    if (r < a.rcnt) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) *(f32x4*)(ob + (long)r * 64 + dt * 16 + g * 4) = acc[u][dt];
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int fbl_attn_rowdot(const void* dO, const void* O, int64_t ld, float* out, int B, int S, int nh,
@@ -1429,7 +1581,7 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
                                  int B, int S, int Sp, int nh, int rcnt, void* stream) {
   if (S < 1 || S > 512 || Sp < S || Sp % 64 || rcnt < 1 || rcnt > 1024) return FBL_ERR_SHAPE;
   if (ldy % 8) return FBL_ERR_ALIGN;
-  if (!X || !Y || !dlo || !dcnt || !out || dcnt_max < 1 || dcnt_max > 8) return FBL_ERR_ARG;
+  if (!X || !Y || !dlo || !dcnt || !out || dcnt_max < 1) return FBL_ERR_ARG;
   if (row0 && !klen) return FBL_ERR_ARG;
   if (E <= 0 || B <= 0 || nh <= 0) return 0;
   for (int e = 0; e < E; ++e)
@@ -1449,6 +1601,16 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
     }
     attr_bytes = pg_smem(Sp);
   }
+  // more than 8 deltas on a table row: the prefix-difference kernel (its own LDS budget)
+  const bool wide = dcnt_max > 8;
+  static int attr_wide = 0;
+  if (wide && pgw_smem(Sp) > attr_wide) {
+    for (const void* fn : {(const void*)pos_grad_wide_kernel<false>, (const void*)pos_grad_wide_kernel<true>}) {
+      hipError_t e1 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pgw_smem(Sp));
+      if (e1 != hipSuccess) return (int)e1;
+    }
+    attr_wide = pgw_smem(Sp);
+  }
   const int nsplit = (rcnt + PG_ROWS - 1) / PG_ROWS;
   for (int e0 = 0; e0 < E; e0 += PG_MAX_E) {
     PosGradArgs a{};
@@ -1463,7 +1625,10 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
     const dim3 grid((unsigned)(((ne * nh + 7) / 8) * 8 * nsplit));
 #define FBL_PG_LAUNCH(NEG_, CM_, NXR_, OCC_) \
   hipLaunchKernelGGL((pos_grad_kernel<NEG_, CM_, NXR_, OCC_>), grid, dim3(PG_THR), smem_bytes, (hipStream_t)stream, a)
-    if (occ3) {
+    if (wide) {
+      if (neg) hipLaunchKernelGGL(pos_grad_wide_kernel<true>, grid, dim3(PG_THR), pgw_smem(Sp), (hipStream_t)stream, a);
+      else hipLaunchKernelGGL(pos_grad_wide_kernel<false>, grid, dim3(PG_THR), pgw_smem(Sp), (hipStream_t)stream, a);
+    } else if (occ3) {
       if (neg) FBL_PG_LAUNCH(true, 3, 5, 3);
       else FBL_PG_LAUNCH(false, 3, 5, 3);
     } else if (dcnt_max <= 3) {

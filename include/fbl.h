@@ -279,15 +279,17 @@ int fbl_disent_attn_probs(const void* q, const void* k, int64_t ldq, const void*
  *                              dST = dS^T; QT = transposed Q (fbl_head_transpose strides y_sh / y_sb / y_sd); PQT = transposed
  *                              PQ [nh][64][span2]; dK bf16 rows (row stride lddk, head h at column h*64).
  *                              lin_span: |i-j| < lin_span => relidx is injective there (identity buckets, = position_buckets/2;
- *                              0 if unknown): those entries are scattered with plain LDS stores instead of atomics. */
+ *                              a clamped table, position_buckets <= 0: att_span - 1; 0 if unknown): those entries are scattered
+ *                              with plain LDS stores instead of atomics. */
 int fbl_attn_rowdot(const void* dO, const void* O, int64_t ld, float* out, int B, int S, int nh, void* stream);
 /* Position-table gradients of E layer executions in one launch, straight from the dS / dS^T tensors of fbl_disent_attn_bwd_ds(pk):
  *   neg = 0: out[e][h][r][d] = dPK = sum_b sum_{(i,j): relidx(i-j) = rmin + r} dS[i,j] * Q[b*S+i, h*64+d]     (X = dS,   Y = q)
  *   neg = 1: out[e][h][r][d] = dPQ = sum_b sum_{(i,j): relidx(i-j) = rmin + r} dS[i,j] * K[b*S+j, h*64+d]     (X = dS^T, Y = k)
  * X, Y: HOST arrays of E device pointers (X[e]: bf16 [B,nh,Sp,Sp]; Y[e]: bf16 rows of stride ldy, packed by row0 if given);
  * dlo / dcnt int16 [rcnt] (device): table row rmin + r collects the deltas i-j in [dlo[r], dlo[r] + dcnt[r]) (relidx is
- * monotone: the inverse of the index vector), dcnt_max = max(dcnt) (host value, 1..8: FBL_ERR_ARG beyond); klen as in
- * fbl_disent_attn_bwd_ds (only the written corner of X is read);
+ * monotone: the inverse of the index vector), dcnt_max = max(dcnt) (host value >= 1; up to 8 the deltas of a row are walked,
+ * beyond 8 every row is a difference of two fp32 prefix sums along the staged rows of X, at a cost independent of dcnt);
+ * klen as in fbl_disent_attn_bwd_ds (only the written corner of X is read);
  * out fp32 [E, nh, rcnt, 64], fully written (no accumulation, no workspace, bit-reproducible).
  * ref: autograd of model/deberta.py:870-918 (c2p / p2c gathers) and :847-853 (the position projections' inputs). */
 int fbl_attn_pos_grad(int neg, const void* const* X, const void* const* Y, int64_t ldy, const int16_t* dlo, const int16_t* dcnt,

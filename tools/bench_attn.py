@@ -12,6 +12,7 @@ executions per launch).
 import math
 import os
 import sys
+import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -55,7 +56,10 @@ QT = torch.empty(nh, 64, B, Sp, dtype=torch.bfloat16, device=dev)
 dS = torch.zeros(B, nh, Sp, Sp, dtype=torch.bfloat16, device=dev)
 dST = torch.zeros(B, nh, Sp, Sp, dtype=torch.bfloat16, device=dev)
 PQT = torch.empty(nh, 64, span2, dtype=torch.bfloat16, device=dev)
-rv = rel_index_vector(S, 256, 512, 256)
+# the relative-position map of the posgrad leg only: POSMAP=position_buckets/max_relative_positions (0/128: a clamped table)
+PB, MR = (int(x) for x in os.environ.get("POSMAP", "256/512").split("/"))
+PMAP = types.SimpleNamespace(position_buckets=PB, max_rel=MR, att_span=PB if PB > 0 else MR)
+rv = rel_index_vector(S, PB, MR, PMAP.att_span)
 rmin, rcnt = int(rv[0]), int(rv[-1]) - int(rv[0]) + 1
 P = 0.1
 LIN = int(os.environ.get('LIN', '128'))
@@ -97,9 +101,8 @@ def bwd_pk():  # kernel A from the saved probabilities + dK in place
 
 
 from frozenbilm_amd.attn_bwd import _delta_ranges  # noqa: E402
-import types  # noqa: E402
 
-dlo, dcnt, dcmax = _delta_ranges(S, types.SimpleNamespace(position_buckets=256, max_rel=512, att_span=256), torch.device(dev))
+dlo, dcnt, dcmax = _delta_ranges(S, PMAP, torch.device(dev), limit=None)
 EPG = int(os.environ.get("EPG", "1"))  # executions per fbl_attn_pos_grad launch (25 = the end-of-backward launch, cold operands)
 dpos = torch.empty(EPG, nh, rcnt, 64, device=dev)
 _xs1 = [dS] + [torch.empty_like(dS).copy_(dS) for _ in range(EPG - 1)]
@@ -140,6 +143,6 @@ prep_r()
 res = {n: timeit(f) for n, f in (("fwd", fwd), ("fwd_save", fwd_save), ("prep", prep), ("bwd_pk", bwd_pk), ("bwd_dq", bwd_dq),
                                  ("prep_r", prep_r), ("bwd_a", bwd_a), ("shear", shear), (f"posgrad_x{EPG}", posgrad))}
 npairs = int(sum(((int(k) + 63) // 64) ** 2 for k in klen.tolist()) * nh)
-tag = f"pairs={npairs} order={order} S={S} B={B} plainmap={os.environ.get('FBL_ATTN_PLAINMAP', '0')} dbg={os.environ.get('FBL_ATTN_DBG', '0')} occ={os.environ.get('FBL_ATTN_OCC', '-')} lin={LIN}"
+tag = f"pairs={npairs} order={order} S={S} B={B} plainmap={os.environ.get('FBL_ATTN_PLAINMAP', '0')} dbg={os.environ.get('FBL_ATTN_DBG', '0')} occ={os.environ.get('FBL_ATTN_OCC', '-')} lin={LIN} posmap={PB}/{MR}"
 print(tag + " | " + "  ".join(f"{n} {t:.1f}us" for n, t in res.items()) + f"  | bwd total without pos_grad (saved P) "
       f"{res['prep'] + res['bwd_pk'] + res['bwd_dq']:.1f}us, (recompute) {res['prep_r'] + res['bwd_a'] + res['bwd_dq'] + res['shear']:.1f}us")
