@@ -1,6 +1,6 @@
 """Benchmark of the FrozenBiLM masked-LM fwd+bwd hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 without a launcher: spawns the N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without a launcher: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one optimizer step of `main.train_one_epoch`'s body on a synthetic WebVid-shape batch already resident in
@@ -11,10 +11,15 @@ Weak scaling: per-GPU batch fixed, value = total samples/s over all ranks.
 
 Head: like `main.train_one_epoch` (main.py:67) the timed step reads only `.loss`; the model computes the prediction head
 on the labelled rows and fills the full [B,S,128100] logits on first access (SURVEY.md section 7 "full logits only when
-asked").  `--full-logits` reads `.logits` in every step (the reference's eager behaviour); the default run also times
+asked").  `--full-logits` reads `.logits` in every step (the reference's eager behaviour); a `--full` run also times
 a few such steps and reports them as `with_full_logits`.  FLOP figures always use the reference-faithful op list.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line: metric, value (samples/s over the timed steps), unit, ms_per_step, higher_is_better, dtype, the
+configuration, and the timeline and loss of the timed steps.  A plain run does only what that headline needs: set-up, pre-warm,
+warm-up, the timed steps, --dump-outputs, the line.  `--full` then also measures the extra objects below (minutes: rocprofv3
+child runs, the CPU oracle, the downstream loops), plus box_calibration, graphed_step, packed_rows, train_one_epoch, videoqa_eval
+and mc_eval; --no-roofline, --no-cpu-baseline, --no-extras and --no-traffic leave parts of it out.  Without --full, roofline,
+cpu_baseline, cpu_baseline_cfg1 and box_calibration are null and the other extra objects are absent.  The extra objects:
   roofline     -- the dominant kernel (gemm8_kernel, the 8-phase 256x256 bf16 MFMA GEMM: ~45 % of the step's kernel time):
                   algorithmic FLOPs of its launches in one step / their summed HIP-event durations (measured live on the
                   launch stream in an instrumented replay of the same step), against the 2.5 PFLOP/s dense bf16 peak.
@@ -110,7 +115,9 @@ def write_outputs(dirpath, arrays, max_elements=DUMP_MAX_ELEMENTS, seed=0):
         np.save(os.path.join(dirpath, name + ".npy"), t.float().cpu().numpy())
 
 
-def main():
+def parse_args(argv=None):
+    """The command line.  Without --full every measurement beyond the headline is off: the --no-* options are set here, so the
+    rest of the script reads one set of switches (with --full they narrow what it runs)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -118,14 +125,19 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--text-len", type=int, default=256)
     ap.add_argument("--layers", type=int, default=24, help="debug only; anything but 24 is reported as a reduced config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need (minutes): box_calibration, "
+                         "roofline with its rocprofv3 traffic passes, the auxiliary legs (with_full_logits, eval_forward, host, "
+                         "graphed_step, packed_rows, train_one_epoch, videoqa_eval, mc_eval) and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and cpu_baseline_cfg1")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline object")
     ap.add_argument("--eval-forward", action="store_true", help="time the eval forward only (reported under its own metric)")
     ap.add_argument("--full-logits", action="store_true", help="read .logits in every timed step (reference-eager head)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the with_full_logits / eval_forward / host side measurements")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the auxiliary legs (with_full_logits / eval_forward / host / ... measurements)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not re-measure roofline.traffic (two short rocprofv3 --pmc child runs of this script); the newest "
-                         "committed profiles/*_traffic.json is reported instead")
+                    help="with --full: do not re-measure roofline.traffic (two short rocprofv3 --pmc child runs of this script); "
+                         "the newest committed profiles/*_traffic.json is reported instead")
     ap.add_argument("--prewarm", type=int, default=PREWARM_STEPS, help=argparse.SUPPRESS)
     ap.add_argument("--no-retry", action="store_true",
                     help="measure in this process (default at --gpus 1: in a child process that is started once more if it dies "
@@ -149,11 +161,18 @@ def main():
                          "n_ans=1000); mc = configs[4] (4-way multiple choice, B=8, S=512)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed to DIR/<name>.npy (float32; see the module docstring)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload != "mlm":
         ap.error("--dump-outputs writes the outputs of the mlm step only")
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_extras = args.no_traffic = True
+    return args
+
+
+def main():
+    args = parse_args()
     if _wants_supervisor(args):
         sys.exit(supervise_single_rank())
     import faulthandler
@@ -298,10 +317,11 @@ def main():
 
     # box calibration (context for the reader, not a result): the pool's boxes differ -- the same tree measured 46.5-47.7 ms per
     # step on most of them and 57.6 on one -- so the line carries what THIS box gives a fixed, well-known launch: the 8-phase
-    # GEMM at 4096^3 (1270-1370 TFLOP/s on a healthy box), right after the timed region.
+    # GEMM at 4096^3 (1270-1370 TFLOP/s on a healthy box), right after the timed region.  --full only, like everything below
+    # that measures more than the headline.
     box = None
     _phase("box calibration")
-    if rank == 0:
+    if rank == 0 and args.full:
         ca = (torch.rand(4096, 4096, device=dev) * 2 - 1).to(torch.bfloat16)
         cb = (torch.rand(4096, 4096, device=dev) * 2 - 1).to(torch.bfloat16)
         co = torch.empty(4096, 4096, dtype=torch.bfloat16, device=dev)

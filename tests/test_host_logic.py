@@ -330,3 +330,18 @@ def test_bench_write_outputs_float32_fixed_sample(tmp_path):
     for n in arrays:
         assert np.array_equal(np.load(tmp_path / "b" / (n + ".npy")), got[n])
     assert (3 * bench.DUMP_MAX_ELEMENTS + 1) * 4 < 64e6  # loss, grads, params, logits
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """bench.py without --full measures nothing the headline does not need: the roofline (and its traffic passes), the
+    auxiliary legs and the CPU baselines are off.  --full turns them on, and the --no-* options still narrow it."""
+    import bench
+
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and (plain.gpus, plain.steps, plain.warmup) == (1, 20, 5)
+    assert plain.no_roofline and plain.no_traffic and plain.no_extras and plain.no_cpu_baseline
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and (full.steps, full.warmup) == (20, 5)
+    assert not (full.no_roofline or full.no_traffic or full.no_extras or full.no_cpu_baseline)
+    narrowed = bench.parse_args(["--full", "--no-cpu-baseline", "--no-traffic"])
+    assert narrowed.no_cpu_baseline and narrowed.no_traffic and not (narrowed.no_roofline or narrowed.no_extras)
