@@ -346,12 +346,13 @@ static bool fork_join_events(hipStream_t s, hipStream_t aux, hipEvent_t* fork, h
 // ---- dispatch of the NT GEMM: a pure plan (which kernel runs which rows on which stream) and the launcher that executes it
 
 // What runs one launch, and its tile (rows x columns)
+// (the ids are public: FBL_GK_* of include/fbl.h, reported by fbl_gemm_plan_launches)
 enum GemmKernel {
-  G8_256, G8_224, G8_128,  // 8-phase kernel (gemm8.hip), 256 columns
-  G8_SPLITK,               // 8-phase 256x256 tiles, K cut into slices of GemmPlan::k8_per K-tiles, partials to the workspace
-  T2_256, T2_224,          // 2-stage kernel, 8 waves, 256 columns
-  T2_128, T2_64_RING,      // 2-stage kernel, 4 waves, 128 columns (the 64-row tiles run the 3-stage ring)
-  T2_128_SPLITK,           // 2-stage 128x128 tiles, partials to the workspace or atomically added to C
+  G8_256 = FBL_GK_G8_256, G8_224 = FBL_GK_G8_224, G8_128 = FBL_GK_G8_128,  // 8-phase kernel (gemm8.hip), 256 columns
+  G8_SPLITK = FBL_GK_G8_SPLITK,  // 8-phase 256x256 tiles, K cut into slices of GemmPlan::k8_per K-tiles, partials to the workspace
+  T2_256 = FBL_GK_T2_256, T2_224 = FBL_GK_T2_224,          // 2-stage kernel, 8 waves, 256 columns
+  T2_128 = FBL_GK_T2_128, T2_64_RING = FBL_GK_T2_64_RING,  // 2-stage kernel, 4 waves, 128 columns (the 64-row tiles: 3-stage ring)
+  T2_128_SPLITK = FBL_GK_T2_128_SPLITK,  // 2-stage 128x128 tiles, partials to the workspace or atomically added to C
 };
 static int tile_rows(GemmKernel k) {
   switch (k) {
@@ -606,15 +607,18 @@ static GemmArgs nt_args(const void* A, int64_t lda, const void* B, int64_t ldb, 
   return g;
 }
 
-// Validates a call, completes its GemmArgs (split-K, dropout, keys of the tail / segment outputs) and runs its plan.
+// Validates a call and completes its GemmArgs (split-K, dropout, keys of the tail / segment outputs); fills in the planner's
+// view of the call.  *empty: nothing to do (M, N or batch <= 0).  Pure host logic apart from the CU count of the current device,
+// which it asks for only when n_cu <= 0.  gemm_nt and fbl_gemm_plan_launches share it, so the query cannot drift from what runs.
 // splitk >= 2 asks for C += A.B^T (atomically, or through splitk_ws when that holds batch*splitk*M*roundup(N,4) floats).
 // p_drop > 0 (ReLU epilogue, the second segment or the adapter tail): dropout of the activated output, element (m, n) keyed by
 // (drop_seed, m*ldc + n).
-static int gemm_nt(GemmArgs g, int batch, int splitk, float* splitk_ws, int64_t splitk_ws_floats, float p_drop, void* stream,
-                   void* aux_stream) {
+static int prepare_gemm(GemmArgs& g, int batch, int splitk, float* splitk_ws, int64_t splitk_ws_floats, float p_drop,
+                        bool aux_stream, int n_cu, GemmCall* c, bool* empty) {
   const int M = g.M, N = g.N, K = g.K;
   const bool tail = g.aux_kind == FBL_AUX_ADAPTER_TAIL;
-  if (M <= 0 || N <= 0 || batch <= 0) return 0;
+  *empty = M <= 0 || N <= 0 || batch <= 0;
+  if (*empty) return 0;
   if (K <= 0 || (K % BK) != 0) return FBL_ERR_SHAPE;               // K must be a multiple of 64 (callers zero-pad)
   if ((g.lda % 8) != 0 || (g.ldb % 8) != 0) return FBL_ERR_ALIGN;  // 16-byte operand rows
   if (splitk < 1) splitk = 1;
@@ -652,8 +656,19 @@ static int gemm_nt(GemmArgs g, int batch, int splitk, float* splitk_ws, int64_t 
     g.drop_thresh = fbl_drop_thresh(p_drop);
     g.drop_inv_keep = 1.f / (1.f - p_drop);
   }
-  const GemmCall c{batch, accumulate, p_drop > 0.f, splitk_ws != nullptr, splitk_ws_floats,
-                   aux_stream != nullptr && aux_stream != stream, device_cu_count()};
+  *c = GemmCall{batch, accumulate, p_drop > 0.f, splitk_ws != nullptr, splitk_ws_floats, aux_stream,
+                n_cu > 0 ? n_cu : device_cu_count()};
+  return 0;
+}
+
+static int gemm_nt(GemmArgs g, int batch, int splitk, float* splitk_ws, int64_t splitk_ws_floats, float p_drop, void* stream,
+                   void* aux_stream) {
+  GemmCall c;
+  bool empty;
+  if (const int rc = prepare_gemm(g, batch, splitk, splitk_ws, splitk_ws_floats, p_drop,
+                                  aux_stream != nullptr && aux_stream != stream, 0, &c, &empty))
+    return rc;
+  if (empty) return 0;
   return run_plan(plan_gemm(g, c), g, batch, (hipStream_t)stream, (hipStream_t)aux_stream);
 }
 
@@ -666,17 +681,63 @@ extern "C" int fbl_gemm_plan(int M, int N, int K, int batch, int splitk) {
   return plan_gemm(nt_args(nullptr, K, nullptr, K, M, N, K), c).big8 ? 8 : 2;
 }
 
+// ---- the GemmArgs of each entry point (shared by the entry point and fbl_gemm_plan_launches)
+
+static int plain_args(GemmArgs* g, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
+                      const float* bias, const float* rowscale, float alpha, int act, int aux_kind, const void* aux,
+                      int64_t ld_aux, float* out_f32, void* out_bf16, void* out_pre_bf16, int64_t ldc, int64_t strideA,
+                      int64_t strideB, int64_t strideC, int64_t strideAux, int64_t strideBias) {
+  if (aux_kind == FBL_AUX_ADAPTER_TAIL) return FBL_ERR_ARG;  // (has its own entry point: fbl_adapter_up_resid_fwd)
+  *g = nt_args(A, lda, B, ldb, M, N, K);
+  g->bias = bias; g->rowscale = rowscale; g->alpha = alpha; g->act = act; g->aux_kind = aux_kind; g->aux = aux; g->ld_aux = ld_aux;
+  g->out_f32 = out_f32; g->out_bf16 = (bf16*)out_bf16; g->out_pre = (bf16*)out_pre_bf16; g->ldc = ldc;
+  g->sA = strideA; g->sB = strideB; g->sC = strideC; g->sAux = strideAux; g->sBias = strideBias;
+  return 0;
+}
+
+static GemmArgs adapter_down_args(const void* x_bf16, int64_t ldx, const void* wd_bf16, int64_t ldw, int M, int A, int K,
+                                  const float* bias, uint64_t seed, const uint64_t* seed_dev, void* z_bf16, int64_t ldz) {
+  GemmArgs g = nt_args(x_bf16, ldx, wd_bf16, ldw, M, A, K);
+  g.bias = bias; g.act = FBL_ACT_RELU; g.out_bf16 = (bf16*)z_bf16; g.ldc = ldz;
+  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  return g;
+}
+
+static int dense_adapter_args(GemmArgs* g, const void* x_bf16, int64_t ldx, const void* wm_bf16, int64_t ldw, int M, int N1,
+                              int A, int K, const float* bias_m, float* y_f32, void* y_bf16, int64_t ldy, uint64_t seed,
+                              const uint64_t* seed_dev, void* z_bf16, int64_t ldz) {
+  if (A <= 0 || (N1 & 63)) return FBL_ERR_ARG;
+  *g = nt_args(x_bf16, ldx, wm_bf16, ldw, M, N1 + A, K);
+  g->bias = bias_m; g->out_f32 = y_f32; g->out_bf16 = (bf16*)y_bf16; g->ldc = ldy;
+  g->seg_n = N1; g->seg_out = (bf16*)z_bf16; g->seg_ld = ldz;
+  g->drop_seed = seed; g->drop_seed_dev = seed_dev;
+  return 0;
+}
+
+static int adapter_tail_args(GemmArgs* g, const void* z_bf16, int64_t ldz, const void* wu_bf16, int64_t ldw, int M, int H,
+                             int A, const float* bias_u, const void* x_bf16, int64_t ldx, float p_drop, uint64_t seed,
+                             const uint64_t* seed_dev, const float* r_t, int64_t ld_r, const float* r_stats,
+                             const float* r_gamma, const float* r_beta, const int32_t* r_rowmask, float* out_t, int64_t ldt) {
+  if (!z_bf16 || !wu_bf16 || !x_bf16 || !r_t || !out_t) return FBL_ERR_ARG;
+  if (p_drop < 0.f || p_drop >= 1.f) return FBL_ERR_ARG;
+  if (ldx % 8) return FBL_ERR_ALIGN;
+  *g = nt_args(z_bf16, ldz, wu_bf16, ldw, M, H, A);
+  g->bias = bias_u; g->aux_kind = FBL_AUX_ADAPTER_TAIL; g->aux = x_bf16; g->ld_aux = ldx; g->out_f32 = out_t; g->ldc = ldt;
+  g->r_t = r_t; g->ld_r = ld_r; g->r_stats = r_stats; g->r_gamma = r_gamma; g->r_beta = r_beta; g->r_rowmask = r_rowmask;
+  g->drop_seed = seed; g->drop_seed_dev = seed_dev;
+  return 0;
+}
+
 extern "C" int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
                                 const float* bias, const float* rowscale, float alpha, int act, int aux_kind,
                                 const void* aux, int64_t ld_aux, float* out_f32, void* out_bf16, void* out_pre_bf16,
                                 int64_t ldc, int batch, int64_t strideA, int64_t strideB, int64_t strideC,
                                 int64_t strideAux, int64_t strideBias, int splitk, float* splitk_ws,
                                 int64_t splitk_ws_floats, void* stream, void* aux_stream) {
-  if (aux_kind == FBL_AUX_ADAPTER_TAIL) return FBL_ERR_ARG;  // (has its own entry point: fbl_adapter_up_resid_fwd)
-  GemmArgs g = nt_args(A, lda, B, ldb, M, N, K);
-  g.bias = bias; g.rowscale = rowscale; g.alpha = alpha; g.act = act; g.aux_kind = aux_kind; g.aux = aux; g.ld_aux = ld_aux;
-  g.out_f32 = out_f32; g.out_bf16 = (bf16*)out_bf16; g.out_pre = (bf16*)out_pre_bf16; g.ldc = ldc;
-  g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sAux = strideAux; g.sBias = strideBias;
+  GemmArgs g;
+  if (const int rc = plain_args(&g, A, lda, B, ldb, M, N, K, bias, rowscale, alpha, act, aux_kind, aux, ld_aux, out_f32,
+                                out_bf16, out_pre_bf16, ldc, strideA, strideB, strideC, strideAux, strideBias))
+    return rc;
   return gemm_nt(g, batch, splitk, splitk_ws, splitk_ws_floats, 0.f, stream, aux_stream);
 }
 
@@ -685,9 +746,7 @@ extern "C" int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64
 extern "C" int fbl_adapter_down_fwd(const void* x_bf16, int64_t ldx, const void* wd_bf16, int64_t ldw, int M, int A, int K,
                                     const float* bias, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* z_bf16,
                                     int64_t ldz, void* stream) {
-  GemmArgs g = nt_args(x_bf16, ldx, wd_bf16, ldw, M, A, K);
-  g.bias = bias; g.act = FBL_ACT_RELU; g.out_bf16 = (bf16*)z_bf16; g.ldc = ldz;
-  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  const GemmArgs g = adapter_down_args(x_bf16, ldx, wd_bf16, ldw, M, A, K, bias, seed, seed_dev, z_bf16, ldz);
   return gemm_nt(g, 1, 1, nullptr, 0, p_drop, stream, nullptr);
 }
 
@@ -702,11 +761,10 @@ extern "C" int fbl_dense_adapter_down_fwd(const void* x_bf16, int64_t ldx, const
                                           int A, int K, const float* bias_m, float* y_f32, void* y_bf16, int64_t ldy,
                                           float p_drop, uint64_t seed, const uint64_t* seed_dev, void* z_bf16, int64_t ldz,
                                           void* stream, void* aux_stream) {
-  if (A <= 0 || (N1 & 63)) return FBL_ERR_ARG;
-  GemmArgs g = nt_args(x_bf16, ldx, wm_bf16, ldw, M, N1 + A, K);
-  g.bias = bias_m; g.out_f32 = y_f32; g.out_bf16 = (bf16*)y_bf16; g.ldc = ldy;
-  g.seg_n = N1; g.seg_out = (bf16*)z_bf16; g.seg_ld = ldz;
-  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  GemmArgs g;
+  if (const int rc = dense_adapter_args(&g, x_bf16, ldx, wm_bf16, ldw, M, N1, A, K, bias_m, y_f32, y_bf16, ldy, seed, seed_dev,
+                                        z_bf16, ldz))
+    return rc;
   return gemm_nt(g, 1, 1, nullptr, 0, p_drop, stream, aux_stream);
 }
 
@@ -715,14 +773,67 @@ extern "C" int fbl_adapter_up_resid_fwd(const void* z_bf16, int64_t ldz, const v
                                         const uint64_t* seed_dev, const float* r_t, int64_t ld_r, const float* r_stats, const float* r_gamma,
                                         const float* r_beta, const int32_t* r_rowmask, float* out_t, int64_t ldt,
                                         void* stream) {
-  if (!z_bf16 || !wu_bf16 || !x_bf16 || !r_t || !out_t) return FBL_ERR_ARG;
-  if (p_drop < 0.f || p_drop >= 1.f) return FBL_ERR_ARG;
-  if (ldx % 8) return FBL_ERR_ALIGN;
-  GemmArgs g = nt_args(z_bf16, ldz, wu_bf16, ldw, M, H, A);
-  g.bias = bias_u; g.aux_kind = FBL_AUX_ADAPTER_TAIL; g.aux = x_bf16; g.ld_aux = ldx; g.out_f32 = out_t; g.ldc = ldt;
-  g.r_t = r_t; g.ld_r = ld_r; g.r_stats = r_stats; g.r_gamma = r_gamma; g.r_beta = r_beta; g.r_rowmask = r_rowmask;
-  g.drop_seed = seed; g.drop_seed_dev = seed_dev;
+  GemmArgs g;
+  if (const int rc = adapter_tail_args(&g, z_bf16, ldz, wu_bf16, ldw, M, H, A, bias_u, x_bf16, ldx, p_drop, seed, seed_dev, r_t,
+                                       ld_r, r_stats, r_gamma, r_beta, r_rowmask, out_t, ldt))
+    return rc;
   return gemm_nt(g, 1, 1, nullptr, 0, p_drop, stream, nullptr);
+}
+
+// The whole plan of one call of an NT GEMM entry point, without running it (include/fbl.h).  The operand pointers the entry
+// points would be given are stand-ins here: never dereferenced, only tested for NULL by the shared validation.
+extern "C" int fbl_gemm_plan_launches(int entry, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ld_aux,
+                                      int seg_n, int act, int aux_kind, int flags, int batch, int splitk, int64_t ws_floats,
+                                      int n_cu, int32_t* out) {
+  if (!out || n_cu <= 0) return FBL_ERR_ARG;
+  static const char stand_in[16] = {};
+  const void* p = stand_in;
+  auto has = [&](int f) { return (flags & f) ? (void*)p : nullptr; };
+  const float p_drop = (flags & FBL_GPQ_DROPOUT) ? 0.5f : 0.f;
+  GemmArgs g;
+  int rc = 0;
+  switch (entry) {
+    case FBL_GEMM_ENTRY_PLAIN:
+      rc = plain_args(&g, p, lda, p, ldb, M, N, K, (const float*)has(FBL_GPQ_BIAS), (const float*)has(FBL_GPQ_ROWSCALE), 1.f,
+                      act, aux_kind, has(FBL_GPQ_AUX), ld_aux, (float*)has(FBL_GPQ_OUT_F32), has(FBL_GPQ_OUT_BF16),
+                      has(FBL_GPQ_OUT_PRE), ldc, 0, 0, 0, 0, 0);
+      if (rc == 0 && p_drop > 0.f) return FBL_ERR_ARG;  // (fbl_gemm_bf16_nt has no dropout)
+      break;
+    case FBL_GEMM_ENTRY_ADAPTER_DOWN:
+      if (batch != 1 || splitk > 1) return FBL_ERR_ARG;
+      g = adapter_down_args(p, lda, p, ldb, M, N, K, (const float*)has(FBL_GPQ_BIAS), 0, nullptr, (void*)p, ldc);
+      break;
+    case FBL_GEMM_ENTRY_DENSE_ADAPTER_DOWN:
+      if (batch != 1 || splitk > 1) return FBL_ERR_ARG;
+      rc = dense_adapter_args(&g, p, lda, p, ldb, M, seg_n, N - seg_n, K, (const float*)has(FBL_GPQ_BIAS),
+                              (float*)has(FBL_GPQ_OUT_F32), has(FBL_GPQ_OUT_BF16), ldc, 0, nullptr, (void*)p, ld_aux);
+      break;
+    case FBL_GEMM_ENTRY_ADAPTER_TAIL:
+      if (batch != 1 || splitk > 1) return FBL_ERR_ARG;
+      rc = adapter_tail_args(&g, p, lda, p, ldb, M, N, K, (const float*)has(FBL_GPQ_BIAS), p, ld_aux, p_drop, 0, nullptr,
+                             (const float*)p, ldc, (const float*)has(FBL_GPQ_R_NORM), (const float*)has(FBL_GPQ_R_NORM),
+                             (const float*)has(FBL_GPQ_R_NORM), nullptr, (float*)p, ldc);
+      break;
+    default:
+      return FBL_ERR_ARG;
+  }
+  if (rc) return rc;
+  GemmCall c;
+  bool empty;
+  rc = prepare_gemm(g, batch, splitk, (flags & FBL_GPQ_WS) ? (float*)p : nullptr, ws_floats, p_drop,
+                    (flags & FBL_GPQ_AUX_STREAM) != 0, n_cu, &c, &empty);
+  if (rc) return rc;
+  for (int i = 0; i < FBL_GEMM_PLAN_OUT_LEN; ++i) out[i] = 0;
+  if (empty) return 0;
+  const GemmPlan pl = plan_gemm(g, c);
+  out[0] = pl.n; out[1] = pl.splitk; out[2] = pl.k8_per; out[3] = pl.fold; out[4] = pl.big8;
+  for (int i = 0; i < pl.n; ++i) {
+    out[5 + 4 * i] = pl.launch[i].kernel;
+    out[6 + 4 * i] = pl.launch[i].row0;
+    out[7 + 4 * i] = pl.launch[i].rows;
+    out[8 + 4 * i] = pl.launch[i].on_aux;
+  }
+  return 0;
 }
 
 extern "C" int fbl_gemm_bf16_tn_acc(const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,

@@ -34,6 +34,7 @@ SIGNATURES = {
     "fbl_adapter_bwd_dw": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "fbl_embed_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "fbl_gemm_plan": (_i, [_i, _i, _i, _i, _i]),
+    "fbl_gemm_plan_launches": (_i, [_i, _i, _i, _i, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _l, _i, _vp]),
     "fbl_ln_fwd": (_i, [_vp, _l, _f, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i,
                         _vp]),
     "fbl_ln_materialize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
@@ -195,6 +196,31 @@ def _rows2d(t: torch.Tensor, name: str):
 def gemm_plan(M, N, K, batch=1, splitk=1):
     """8 if fbl_gemm_bf16_nt runs this plain problem on the 8-phase kernel (gemm8_kernel), 2 for the 2-stage kernel"""
     return load().fbl_gemm_plan(int(M), int(N), int(K), int(batch), int(splitk))
+
+
+# include/fbl.h: kernel ids (FBL_GK_*), entry points (FBL_GEMM_ENTRY_*) and option bits (FBL_GPQ_*) of fbl_gemm_plan_launches
+GK_NAMES = ("G8_256", "G8_224", "G8_128", "G8_SPLITK", "T2_256", "T2_224", "T2_128", "T2_64_RING", "T2_128_SPLITK")
+ENTRY_PLAIN, ENTRY_ADAPTER_DOWN, ENTRY_DENSE_ADAPTER_DOWN, ENTRY_ADAPTER_TAIL = 0, 1, 2, 3
+GPQ = dict(out_f32=1, out_bf16=2, out_pre=4, bias=8, rowscale=16, aux=32, dropout=64, ws=128, aux_stream=256, r_norm=512)
+
+
+def gemm_plan_launches(entry, M, N, K, *, lda=None, ldb=None, ldc=None, ld_aux=0, seg_n=0, act=ACT_NONE, aux_kind=AUX_NONE,
+                       opts=(), batch=1, splitk=1, ws_floats=0, n_cu=256):
+    """What an NT GEMM entry point would launch (pure host logic).  opts: names of GPQ bits.  Returns (code, plan): code 0
+    and plan = dict(launches=[(kernel name, row0, rows, on_aux), ...], splitk, k8_per, fold, big8), or the FBL_ERR_* code
+    the call would return and None."""
+    flags = 0
+    for o in opts:
+        flags |= GPQ[o]
+    out = (C.c_int32 * 13)()
+    code = load().fbl_gemm_plan_launches(int(entry), int(M), int(N), int(K), int(K if lda is None else lda),
+                                         int(K if ldb is None else ldb), int(N if ldc is None else ldc), int(ld_aux),
+                                         int(seg_n), int(act), int(aux_kind), flags, int(batch), int(splitk), int(ws_floats),
+                                         int(n_cu), out)
+    if code:
+        return code, None
+    launches = [(GK_NAMES[out[5 + 4 * i]], out[6 + 4 * i], out[7 + 4 * i], bool(out[8 + 4 * i])) for i in range(out[0])]
+    return 0, dict(launches=launches, splitk=out[1], k8_per=out[2], fold=bool(out[3]), big8=bool(out[4]))
 
 
 def gemm(A, B, *, bias=None, rowscale=None, alpha=1.0, act=ACT_NONE, aux=None, aux_kind=AUX_NONE, out_f32=None,

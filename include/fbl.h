@@ -76,6 +76,42 @@ int fbl_gemm_bf16_nt(const void* A, int64_t lda, const void* B, int64_t ldb, int
  * for the big ones).  bench.py attributes launches to the dominant kernel with it. */
 int fbl_gemm_plan(int M, int N, int K, int batch, int splitk);
 
+/* The kernel configurations an NT GEMM launch can run on (rows x columns of its tile). */
+enum {
+  FBL_GK_G8_256 = 0,        /* 8-phase kernel (gemm8_kernel), 256x256 */
+  FBL_GK_G8_224 = 1,        /* 8-phase, 224x256 */
+  FBL_GK_G8_128 = 2,        /* 8-phase, 128x256 */
+  FBL_GK_G8_SPLITK = 3,     /* 8-phase 256x256, K in slices, partial tiles to the workspace */
+  FBL_GK_T2_256 = 4,        /* 2-stage kernel, 256x256 */
+  FBL_GK_T2_224 = 5,        /* 2-stage, 224x256 */
+  FBL_GK_T2_128 = 6,        /* 2-stage, 128x128 */
+  FBL_GK_T2_64_RING = 7,    /* 3-stage ring, 64x128 */
+  FBL_GK_T2_128_SPLITK = 8  /* 2-stage 128x128, K split, partials to the workspace or atomically added to C */
+};
+/* The entry points built on the NT GEMM, and the option bits of fbl_gemm_plan_launches. */
+enum {
+  FBL_GEMM_ENTRY_PLAIN = 0,              /* fbl_gemm_bf16_nt */
+  FBL_GEMM_ENTRY_ADAPTER_DOWN = 1,       /* fbl_adapter_down_fwd:       N = A, ldc = ldz */
+  FBL_GEMM_ENTRY_DENSE_ADAPTER_DOWN = 2, /* fbl_dense_adapter_down_fwd: N = N1 + A, seg_n = N1, ldc = ldy, ld_aux = ldz */
+  FBL_GEMM_ENTRY_ADAPTER_TAIL = 3        /* fbl_adapter_up_resid_fwd:   N = H, K = A, ldc = ldt = ld_r, ld_aux = ldx */
+};
+enum {
+  FBL_GPQ_OUT_F32 = 1, FBL_GPQ_OUT_BF16 = 2, FBL_GPQ_OUT_PRE = 4, /* which outputs the call passes (plain; dense: y_f32 / y_bf16) */
+  FBL_GPQ_BIAS = 8, FBL_GPQ_ROWSCALE = 16, FBL_GPQ_AUX = 32,       /* which optional operands it passes */
+  FBL_GPQ_DROPOUT = 64,     /* p_drop > 0 */
+  FBL_GPQ_WS = 128,         /* a split-K workspace pointer is passed (ws_floats: its size) */
+  FBL_GPQ_AUX_STREAM = 256, /* an aux stream distinct from `stream` is passed */
+  FBL_GPQ_R_NORM = 512      /* adapter tail: the LayerNorm-normalised residual (r_stats, r_gamma, r_beta) */
+};
+#define FBL_GEMM_PLAN_OUT_LEN 13
+/* Host-side query, no launch, no HIP call: what the entry point `entry` would launch for this call on a device of n_cu CUs.
+ * It runs the entry point's own validation and planner.  Returns the FBL_ERR_* code the call would return, or 0 and
+ * out[FBL_GEMM_PLAN_OUT_LEN] = { n launches (0: nothing to do), splitk, k8_per, fold (the workspace is folded into C after
+ * the launches), big8 (what fbl_gemm_plan reports), then per launch in launch order: kernel (FBL_GK_*), row0, rows, on_aux }.
+ * Arguments that do not apply to an entry point are ignored (batch and splitk must then be 1). */
+int fbl_gemm_plan_launches(int entry, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ld_aux, int seg_n,
+                           int act, int aux_kind, int flags, int batch, int splitk, int64_t ws_floats, int n_cu, int32_t* out);
+
 /* Adapter down-projection with the whole bottleneck non-linearity in the GEMM epilogue:
  *   z[M, A] = dropout_p( relu( x[M,K] . Wd[A,K]^T + bd ) )        (bf16 MFMA, fp32 accumulate, bf16 out)
  * Dropout is the counter-based one of fbl_dropout_bf16: element (m, a) is keyed by (seed, m*ldz + a), dropped elements

@@ -26,11 +26,13 @@ def libpath():
     return build_lib(verbose=False)
 
 
-def test_header_and_binding_agree(libpath):
+def test_header_and_binding_agree_on_47_exports(libpath):
+    """include/fbl.h and lib.SIGNATURES declare the same 47 entry points (46 + the plan query fbl_gemm_plan_launches) with the
+    same argument counts and return types."""
     from frozenbilm_amd import lib
 
     decl = declared_functions()
-    assert len(decl) == 46
+    assert len(decl) == 47
     assert set(decl) == set(lib.SIGNATURES), set(decl) ^ set(lib.SIGNATURES)
     for name, (ret, nargs) in decl.items():
         res, argtypes = lib.SIGNATURES[name]

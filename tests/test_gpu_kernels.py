@@ -42,8 +42,9 @@ def close(got, ref, rtol, atol, name=""):
                                    (130, 6, 64), (4100, 2052, 128), (8512, 1536, 192), (4100, 3584, 128), (8512, 192, 1536),
                                    (2100, 70, 64), (4100, 3500, 256), (4100, 3584, 1536), (8512, 6144, 384), (8512, 1536, 384), (4100, 2052, 256),
                                    (4100, 4608, 256), (4100, 4500, 192), (2500, 8192, 128), (8512, 6144, 1536), (691, 16500, 256)])
-# the last four: more than one round of 256x256 tiles (skewed single launch / whole rounds + remainder rows), K = 4, 3, 2 and
-# 24 K-tiles (3 and 2: below the 8-phase kernel's shortest pipeline -> 2-stage 256x256 tiles), ragged last tile column / row;
+# the last four: more than one round of 256x256 tiles (whole rounds + remainder rows), K = 4, 3, 2 and 24 K-tiles (3 and 2:
+# below the 8-phase kernel's shortest pipeline -> 2-stage 256x256 tiles; (2500,8192): 128x128 remainder tiles), ragged last
+# tile column / row;
 # (4100,35xx,K>=256): the 8-phase 256x256 kernel (gemm8.hip; K = 256 is its shortest pipeline, N = 3500 a ragged last column
 # tile); (8512,6144): 8-phase tiles for the whole rounds + 64x128 tiles for the remaining rows (helper stream); (8512,1536,384) and
 # (4100,2052,256): 224-row 8-phase tiles (second wave row with three 16-row MFMA tiles per half);
@@ -168,7 +169,8 @@ def test_gemm_asymmetric_identity(L):
 @pytest.mark.parametrize("M,N,K", [(300, 256, 128), (4100, 2052, 64), (4100, 3584, 64), (4100, 192, 128), (4100, 3584, 256), (4100, 2052, 256),
                                    (4100, 4608, 320)])
 # 128x128, 224x256, 256x256 and 64x128 tiles, 8-phase 256x256, 8-phase 224x256 (plain / residual-add) + its fallbacks,
-# a multi-round problem with an odd number of K-tiles (306 tiles of 256x256, K = 320: 2-stage 256x256 tiles)
+# a multi-round problem with an odd number of K-tiles (306 tiles of 256x256, K = 320: whole rounds on 2-stage 256x256 tiles,
+# the remaining rows on 64x128 tiles)
 def test_gemm_epilogues(L, M, N, K):
     A, B = bf(rnd(M, K, seed=1)).to(BF16), bf(rnd(N, K, seed=2, scale=0.1)).to(BF16)
     bias = rnd(N, seed=3)
@@ -973,10 +975,11 @@ def test_mask_tokens_device(L):
 
 
 @pytest.mark.parametrize("M,N1,A,K", [(300, 128, 16, 128), (4100, 1536, 192, 256), (8512, 1536, 192, 1536), (1000, 768, 96, 3072),
-                                      (2500, 192, 24, 128), (4100, 1152, 144, 256)])
-# small tiles; 8-phase 256x256 tiles (7th tile column = the bottleneck); the Wo shape of the step; a mid-size one;
-# N1 = 192 (a multiple of 64 only); N1 = 1152 = 4.5 x 256: big-tile shape whose boundary would cut a wave's two 32-column
-# ranges -> must run on the narrow tiles
+                                      (2500, 192, 24, 128), (4100, 1152, 144, 256), (8512, 1152, 144, 256)])
+# small tiles; 128x128 tiles (4100 rows: 119 big tiles would leave half the chip idle); the Wo shape of the step on 8-phase
+# 256x256 tiles (7th tile column = the bottleneck); a mid-size one; N1 = 192 (a multiple of 64 only; 64x128 tiles); N1 = 1152 =
+# 4.5 x 256 at 4100 rows (128x128 tiles) and at 8512 rows: a big-tile shape whose boundary would cut a wave's two 32-column
+# ranges -> must run on the narrow tiles (tests/test_gemm_plan.py checks these routes)
 def test_dense_adapter_down_merged(L, M, N1, A, K):
     """fbl_dense_adapter_down_fwd: y = x.W^T + b and z = dropout(relu(y.Wd^T + bd)) from ONE GEMM against [W ; Wd.W]."""
     x = bf(rnd(M, K, seed=1)).to(BF16)
