@@ -78,6 +78,14 @@ SIGNATURES = {
     "fbl_heads_to_rows_bf16": (_i, [_vp, _vp, _i, _i, _i, _l, _vp]),
 }
 
+# the BERT variant's fused attention (include/fbl_mha.h): same library, a table of its own so that SIGNATURES keeps mirroring
+# include/fbl.h exactly
+MHA_SIGNATURES = {
+    "fbl_mha_fwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _i, _i, _i, _vp]),
+    "fbl_mha_bwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l, _vp, _l,
+                         _i, _i, _i, _vp]),
+}
+
 _LIB = None
 
 
@@ -92,7 +100,7 @@ def load(path: Optional[str] = None):
             f"{p} not found: the FrozenBiLM MI355X path needs its HIP library (python -m frozenbilm_amd.build); "
             "there is no CPU/eager fallback")
     lib = C.CDLL(p)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -745,3 +753,31 @@ def dropout_bf16_(x, p_drop, seed):
     _req(x, torch.bfloat16, "x")
     assert x.is_contiguous()
     _chk(load().fbl_dropout_bf16(_p(x), float(p_drop), int(seed), _seed_dev(), x.numel(), _stream()), "fbl_dropout_bf16")
+
+
+# ------------------------------------------------------------------------------------------------ BERT attention (fbl_mha.h)
+def mha_fwd(q, k, v, mask, scale, ctx, lse, B, S, nh, p_drop=0.0, seed=0, klen=None, border=None):
+    """ctx [B*S, >= nh*64] bf16 rows, lse fp32 [B,nh,S]: softmax(scale*Q.K^T + (1-mask)*-10000) . V per head"""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx")):
+        _req(t, torch.bfloat16, n)
+    _req(mask, torch.int32, "mask"); _req(lse, torch.float32, "lse")
+    assert mask.is_contiguous() and mask.numel() == B * S and lse.is_contiguous() and lse.numel() == B * nh * S
+    for t in (klen, border):
+        if t is not None:
+            _req(t, torch.int32, "klen/border")
+            assert t.is_contiguous() and t.numel() == B
+    _chk(load().fbl_mha_fwd(_p(q), _rows2d(q, "q"), _p(k), _rows2d(k, "k"), _p(v), _rows2d(v, "v"), _p(mask), _p(klen), _p(border),
+                            float(scale), float(p_drop), int(seed), _seed_dev(), _p(ctx), _rows2d(ctx, "ctx"), _p(lse), B, S, nh,
+                            _stream()), "fbl_mha_fwd")
+
+
+def mha_bwd(q, k, v, dO, mask, lse, Dv, scale, dQ, dK, dV, B, S, nh, p_drop=0.0, seed=0, klen=None, border=None):
+    """dQ / dK / dV bf16 rows (every row < B*S written); Dv fp32 [B,nh,S] = attn_rowdot(dO, ctx)"""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (dO, "dO"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")):
+        _req(t, torch.bfloat16, n)
+    _req(mask, torch.int32, "mask"); _req(lse, torch.float32, "lse"); _req(Dv, torch.float32, "Dv")
+    assert mask.numel() == B * S and lse.numel() == B * nh * S and Dv.numel() == B * nh * S
+    _chk(load().fbl_mha_bwd(_p(q), _rows2d(q, "q"), _p(k), _rows2d(k, "k"), _p(v), _rows2d(v, "v"), _p(dO), _rows2d(dO, "dO"),
+                            _p(mask), _p(klen), _p(border), _p(lse), _p(Dv), float(scale), float(p_drop), int(seed), _seed_dev(),
+                            _p(dQ), _rows2d(dQ, "dQ"), _p(dK), _rows2d(dK, "dK"), _p(dV), _rows2d(dV, "dV"), B, S, nh, _stream()),
+         "fbl_mha_bwd")

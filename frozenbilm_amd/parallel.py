@@ -88,6 +88,8 @@ class GradReducer:
         load_state_dict / .to() / set_answer_embeddings, which in the reference flow all happen AFTER the optimizer and
         the reducer are created (main.py:182 vs :235, videoqa.py:381); ``model.engine()`` re-binds the reducer then."""
         eng = model.engine()
+        if not hasattr(eng, "bucket_ends"):
+            raise NotImplementedError(f"data-parallel gradient reduction is not implemented for {type(model).__name__}")
         red = cls(eng.flat_grad, eng.bucket_ends, group=group, flat_full=getattr(eng, "flat_grad_full", None), **kw)
         eng.reducer = red
         model._reducer = red
