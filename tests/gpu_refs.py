@@ -1,4 +1,6 @@
-"""Plain-torch fp32 references of the individual ops (test infrastructure only; run on the GPU for speed)."""
+"""Plain-torch references of the individual ops (test infrastructure only; run on the GPU for speed): fp32 for attention
+(ref_attention), float64 for the row ops (ref_ln_fwd, ref_ln_bwd, ref_ce, ref_adam, ref_gelu / ref_dgelu), each computed from
+the very input bits the kernel gets (fp32 and bf16 inputs widened, never re-rounded)."""
 import math
 
 import numpy as np
@@ -49,3 +51,94 @@ def stats(name, got, ref):
     err = (got - ref).abs()
     return (f"{name}: max_abs_err={err.max().item():.3e} mean_abs_err={err.mean().item():.3e} "
             f"ref_absmax={ref.abs().max().item():.3e} ref_std={ref.std().item():.3e}")
+
+
+# ------------------------------------------------------------------------------------------------ float64 row-op references
+def ref_ln_fwd(*, y=None, keep=None, r_plain=None, r_norm=None, gamma, beta, eps, rowmask=None):
+    """fbl_ln_fwd in float64: t = dropout(y) + r_plain + LN_r(r_t) * r_rowmask, out = LN(t) * rowmask.
+    keep: multiplicative dropout mask of y (0 or 1/(1-p)); r_norm = (t, stats [N,2] = (mean, rstd), gamma, beta, rowmask|None).
+    Returns dict(t, mean, rstd, out, ax) -- ax = sum of the magnitudes of t's addends (what one fp32 rounding of t scales with)."""
+    t, ax = 0.0, 0.0
+    if y is not None:
+        a = y.double() * (keep.double() if keep is not None else 1.0)
+        t, ax = t + a, ax + a.abs()
+    if r_plain is not None:
+        t, ax = t + r_plain.double(), ax + r_plain.double().abs()
+    if r_norm is not None:
+        rt, rs, rg, rb, rm = r_norm
+        st = rs.double()
+        m = rm.double()[:, None] if rm is not None else 1.0
+        t = t + ((rt.double() - st[:, :1]) * st[:, 1:] * rg.double()[None] + rb.double()[None]) * m
+        ax = ax + ((rt.double().abs() + st[:, :1].abs()) * st[:, 1:].abs() * rg.double().abs()[None] + rb.double().abs()[None]) * m
+    H = t.shape[1]
+    mean = t.sum(1, keepdim=True) / H
+    var = ((t - mean) ** 2).sum(1, keepdim=True) / H
+    rstd = 1.0 / torch.sqrt(var + float(np.float32(eps)))
+    om = rowmask.double()[:, None] if rowmask is not None else 1.0
+    out = ((t - mean) * rstd * gamma.double()[None] + beta.double()[None]) * om
+    return dict(t=t, mean=mean[:, 0], rstd=rstd[:, 0], out=out, ax=ax)
+
+
+def ref_ln_materialize(t, stats, gamma, beta, rowmask=None, add_bcast=None, S=1):
+    """fbl_ln_materialize in float64 from the given t / stats bits; returns (out, mag) -- mag: magnitudes of the terms"""
+    st = stats.double()
+    om = rowmask.double()[:, None] if rowmask is not None else 1.0
+    c = (t.double() - st[:, :1]) * st[:, 1:] * gamma.double()[None]
+    out = (c + beta.double()[None]) * om
+    mag = ((t.double().abs() + st[:, :1].abs()) * st[:, 1:].abs() * gamma.double().abs()[None] + beta.double().abs()[None]) * om
+    if add_bcast is not None:
+        p = add_bcast.double()[torch.arange(t.shape[0], device=t.device) % S]
+        out, mag = out + p, mag + p.abs()
+    return out, mag + out.abs()
+
+
+def ref_ln_bwd(dout, t, stats, gamma, rowmask=None, keep=None):
+    """fbl_ln_bwd in float64 from the given (t, stats) bits.  Returns dict: dt, dy (= dt * keep), the per-row terms of the
+    three column sums (tg = dout*mask*xhat, tb = dout*mask, dy), and mag = rstd * (|g| + mean|g| + |xhat| mean|g xhat|), the scale of dt."""
+    st = stats.double()
+    mean, rstd = st[:, :1], st[:, 1:]
+    om = rowmask.double()[:, None] if rowmask is not None else 1.0
+    dd = dout.double() * om
+    xh = (t.double() - mean) * rstd
+    g = dd * gamma.double()[None]
+    H = t.shape[1]
+    s1 = g.sum(1, keepdim=True) / H
+    s2 = (g * xh).sum(1, keepdim=True) / H
+    dt = rstd * (g - s1 - xh * s2)
+    dy = dt * keep.double() if keep is not None else dt
+    # (the means of |g| and |g xhat|, not |s1| and |s2|: a row sum that cancels is still only as good as the sum of its magnitudes)
+    mag = rstd.abs() * (g.abs() + g.abs().sum(1, keepdim=True) / H + xh.abs() * (g * xh).abs().sum(1, keepdim=True) / H)
+    return dict(dt=dt, dy=dy, tg=dd * xh, tb=dd, mag=mag, xh=xh)
+
+
+def ref_ce(logits, labels):
+    """float64 cross entropy of logits [N, V] (the V real columns) with ignore label < 0.
+    Returns dict(lse [N], p [N, V] softmax, terms [N] = lse - logit[label] (0 on ignored rows), count)"""
+    x = logits.double()
+    lse = torch.logsumexp(x, 1)
+    lab = labels.long()
+    on = lab >= 0
+    xl = x.gather(1, lab.clamp(min=0)[:, None])[:, 0]
+    terms = torch.where(on, lse - xl, torch.zeros_like(lse))
+    return dict(lse=lse, x=x, terms=terms, count=int(on.sum()), on=on)
+
+
+def ref_adam(p, g, m, v, *, lr, b1, b2, eps, wd, step, clip):
+    """one fbl_adam_flat step in float64 (torch.optim.Adam's formula, L2 weight decay folded into the gradient); in place"""
+    gi = g * clip
+    if wd != 0.0:
+        gi = gi + wd * p
+    m.mul_(b1).add_(gi, alpha=1.0 - b1)
+    v.mul_(b2).add_(gi * gi, alpha=1.0 - b2)
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    p.sub_((lr / bc1) * (m / (v.sqrt() / math.sqrt(bc2) + eps)))
+
+
+def ref_gelu(x):
+    x = x.double()
+    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def ref_dgelu(x):
+    x = x.double()
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
