@@ -14,6 +14,8 @@ by whether the training forward saved its probabilities (sv.psave, engine option
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass, field
+from typing import Optional
 
 import torch
 
@@ -80,8 +82,9 @@ def disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk, defer_pos=False):
     q, k, v = qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:]
     pq, pk = sv.pqk[:, :H], sv.pqk[:, H:]
     relidx = eng.relidx(S)
-    klen = getattr(run, "klen", None)
-    border = getattr(run, "border", None)
+    # This is also the kernel-level entry that the kernel tests and tools/pmc_attn.py drive with bare stand-ins for `run` and
+    # `sv` (B, S, p_att, mask_i32, klen / qkv, pqk, ctx, lse, seed_att): what only an engine step carries is optional here.
+    klen, border = run.klen, getattr(run, "border", None)
     scale = 1.0 / math.sqrt(64 * 3)
     pk_ = getattr(run, "pk", None)
     row0 = pk_.row0 if pk_ is not None else None  # packed-row layout of q / k / v / dO and of the dQ / dK / dV outputs
@@ -143,17 +146,37 @@ def pos_table_grads(eng, st):
     return dpos
 
 
-def pos_chain_buffers(eng, run, n_exec):
-    """The per-step lists that collect, execution by execution, what the position-table gradients of ALL layer executions
-    need: dS / dS^T (2 x 157 MB per execution at the bench shape, kept until the end of backward) and the token rows of the
-    saved q / k."""
+@dataclass
+class PosChain:
+    """What the position-table gradients of ALL layer executions need, collected execution by execution: dS / dS^T (2 x 157 MB
+    per execution at the bench shape, kept until the end of backward) and the token rows of the saved q / k."""
+    rmin: int
+    rcnt: int
+    B: int
+    S: int
+    Sp: int
+    dS: list = field(default_factory=list)
+    dST: list = field(default_factory=list)
+    q: list = field(default_factory=list)
+    k: list = field(default_factory=list)
+    seeds: list = field(default_factory=list)   # seed of each execution's position dropout
+    klen: Optional[torch.Tensor] = None         # the same for every execution of a step
+    row0: Optional[torch.Tensor] = None
+
+    def add(self, st, seed_pos):
+        """st: the state disent_attn_bwd(defer_pos=True) returned for one execution"""
+        self.dS.append(st["dS"]); self.dST.append(st["dST"]); self.q.append(st["q"]); self.k.append(st["k"])
+        self.seeds.append(seed_pos)
+        self.klen, self.row0 = st["klen"], st["row0"]
+
+
+def pos_chain_buffers(eng, run):
+    """an empty PosChain for the backward of `run`"""
     rmin, rcnt = _relidx_range(run.S, eng.cfg)
-    Sp = (run.S + 63) // 64 * 64
-    return dict(X1=[], X2=[], Yq=[], Yk=[], rmin=rmin, rcnt=rcnt, B=run.B, S=run.S, Sp=Sp, n=0, seeds=[], cap=n_exec, klen=None,
-                row0=None)
+    return PosChain(rmin=rmin, rcnt=rcnt, B=run.B, S=run.S, Sp=(run.S + 63) // 64 * 64)
 
 
-def pos_table_grads_batched(eng, run, pc):
+def pos_table_grads_batched(eng, run, pc: PosChain):
     """The relative-position-table gradient of the whole backward pass in five launches at its END (it feeds only
     encoder.LayerNorm's gamma / beta, the last thing backward needs): until round 4 every layer execution ran its own chain
     (two split-K products, folds, cast, projection, dropout, accumulation) on a side stream next to the following layer's GEMMs
@@ -164,20 +187,20 @@ def pos_table_grads_batched(eng, run, pc):
         dR       = sum_e dropout_e(dR_e)                                    (fbl_dropout_sum_f32: each through its own mask)
     Returns dR [span2, H] fp32.  autograd of model/deberta.py:779, 847-853, 870-918 summed over the executions."""
     H, nh, span2 = eng.H, eng.nh, eng.span2
-    E, rmin, rcnt, B, Sp = pc["n"], pc["rmin"], pc["rcnt"], pc["B"], pc["Sp"]
+    E, rmin, rcnt, B, Sp = len(pc.seeds), pc.rmin, pc.rcnt, pc.B, pc.Sp
     dev = eng.dev
     # [dPQ | dPK] of every execution, rows rmin .. rmin + rcnt of the tables (the others cannot be touched: their gradient is
     # zero): bf16 operand of the projection, fully written by the two copies below
     dpb = torch.empty(E, rcnt, 2 * H, dtype=BF16, device=dev)
-    dlo, dcnt, cmax = _delta_ranges(pc["S"], eng.cfg, dev, limit=None)
-    for neg, kx, ky, col0 in ((0, "X1", "Yq", H), (1, "X2", "Yk", 0)):
+    dlo, dcnt, cmax = _delta_ranges(pc.S, eng.cfg, dev, limit=None)
+    for neg, X, Y, col0 in ((0, pc.dS, pc.q, H), (1, pc.dST, pc.k, 0)):
         d = torch.empty(E, nh, rcnt, 64, dtype=F32, device=dev)
-        L.attn_pos_grad(neg, pc[kx][:E], pc[ky][:E], dlo, dcnt, cmax, d, B, pc["S"], Sp, nh, rcnt, klen=pc["klen"], row0=pc["row0"])
+        L.attn_pos_grad(neg, X, Y, dlo, dcnt, cmax, d, B, pc.S, Sp, nh, rcnt, klen=pc.klen, row0=pc.row0)
         # [e, h, r, 64] fp32 -> [e, r, h*64 + .] bf16, into this table's column block
         L.heads_to_rows_bf16(d, dpb[:, :, col0:col0 + H])
     tmp = torch.empty(E, rcnt, H, dtype=F32, device=dev)
     L.gemm(dpb, eng.WposT_exec[:E], out_f32=tmp)
     dR = L.zeros(span2, H, dtype=F32, device=dev)
     # (dropout keys of the [span2, H] table: element (r, c) <-> r*H + c)
-    L.dropout_sum_f32(tmp, pc["seeds"][:E] if run.p_hid > 0 else [0] * E, run.p_hid, dR[rmin:rmin + rcnt], key0=rmin * H)
+    L.dropout_sum_f32(tmp, pc.seeds if run.p_hid > 0 else [0] * E, run.p_hid, dR[rmin:rmin + rcnt], key0=rmin * H)
     return dR

@@ -252,7 +252,7 @@ class BertEngine:
             Vout, table, bias = self.V, self.Eb, self.head_bias
         ldv = _ru(Vout, 64)
         run.Vout, run.head_table, run.head_bias, run.ldv, run.use_ans = Vout, table, bias, ldv, use_ans
-        rows_only = getattr(run, "logit_rows", None)
+        rows_only = run.logit_rows
         if rows_only is not None:
             hin = torch.empty(rows_only.numel(), H, dtype=BF16, device=dev)
             if rows_only.numel():
@@ -287,7 +287,7 @@ class BertEngine:
         return logits, run.loss_acc[0] / run.loss_acc[1]
 
     def fill_logits(self, run):
-        if getattr(run, "logits_pending", False):
+        if run.logits_pending:
             run.logits_pending = False
             L.gemm(run.head_ln_bf16, run.head_table, bias=run.head_bias, out_f32=run.logits, N=run.Vout)
 

@@ -65,6 +65,45 @@ class Packing:
     n: int               # Np
 
 
+@dataclass
+class MergedPack:
+    """What the merged adapters of one site type (attention output / FFN output) share over the layers, all in reverse layer
+    order (j = nL-1-layer): a dense layer followed by an adapter runs as ONE GEMM against [W ; Wd.W]
+    (fbl_dense_adapter_down_fwd); the composed rows Wd.W change with every optimizer step (_compose_adapter_down)."""
+    A: int
+    WT: torch.Tensor                # bf16 [nL, K, H]: W^T of the frozen dense layer
+    WM: torch.Tensor                # bf16 [nL, H + A, K]: [W ; Wd.W]
+    bM: torch.Tensor                # fp32 [nL, H + A]: [b ; Wd.b + bd]
+    b16: torch.Tensor               # bf16 [nL, 1, H]: b as a GEMM operand
+    WF: Optional[torch.Tensor]      # bf16 [nL, H, Kf]: [W^T | (Wd.W)^T | 0] of the folded backward (attention output only)
+    groups: list                    # (j0, layers, offset of down.weight, of down.bias, stride) per strided batch, layer 0 first
+
+
+@dataclass
+class AdapterSite:
+    """One adapter of one layer.  Built once: every tensor is a view of the flat parameter buffers or of a pack that never
+    moves (captured graphs keep reading them); only upT / downT are per step.  The routes follow from the shapes:
+      merged   dense + down-projection as one GEMM, fused tail, and (attention output) dx folded into the dense dX GEMM: needs
+               the bottleneck unpadded, A % 64 == 0, and the segment boundary H on a wave's column range, H % 64 == 0
+               (include/fbl.h); otherwise neither the composed weights nor their per-step rebuild exist
+      grouped  weight-gradient products parked for a grouped launch (fbl_adapter_bwd_dw takes Ap <= 256 and H % 8 == 0);
+               otherwise launched per adapter on the side stream (_adapter_bwd)"""
+    name: str
+    A: int
+    Ap: int                                   # A rounded up to 64
+    down: torch.Tensor                        # bf16 [A, H]
+    up: torch.Tensor                          # bf16 [H, Ap]: the parameter's bf16 copy, or a zero-padded copy of it when Ap != A
+    bd: torch.Tensor                          # fp32 [A]
+    bu: torch.Tensor                          # fp32 [H]
+    merged: bool
+    grouped: bool
+    WM: Optional[torch.Tensor] = None         # merged: this layer's rows of MergedPack.WM / .bM / .WF
+    bM: Optional[torch.Tensor] = None
+    WF: Optional[torch.Tensor] = None
+    upT: Optional[torch.Tensor] = None        # bf16 [A, H] / [H, Ap]: operands of the adapter backward, rebuilt on first use
+    downT: Optional[torch.Tensor] = None      # after every refresh (_adapter_bwd_operands)
+
+
 class Engine:
     def __init__(self, model):
         self.m = model
@@ -87,17 +126,29 @@ class Engine:
                                "there is no CPU fallback")
         L.load()
         self.dev = dev
-        self.opts = dict(getattr(model, "engine_options", None) or {})
-        unknown = set(self.opts) - {"eager_logits", "side_stream", "fold_dx", "dw_on_side", "fuse_tail", "merge", "dw_group", "attn_save_p"}
+        # Engine options: `model.engine_options` (a dict read ONCE, when the engine is built; the product reads no environment
+        # variable).  Defaults are the shipped configuration.  None of them picks an adapter route: those follow from the
+        # shapes alone (AdapterSite.merged / .grouped).
+        o = dict(getattr(model, "engine_options", None) or {})
+        unknown = set(o) - {"eager_logits", "dw_group", "attn_save_p"}
         if unknown:
             raise ValueError(f"unknown engine_options: {sorted(unknown)}")
+        #   eager_logits   fill the full [N, V] logits in every forward even when only the loss is consumed (reference-eager)
+        self.eager_logits = bool(o.get("eager_logits", False))
+        #   attn_save_p    False = the attention backward recomputes the probabilities and forms dK by the key-major shear pass
+        #                  instead of reading the ones the training forward saved (157 MB per layer execution at the bench shape,
+        #                  held until the backward)
+        self.attn_save_p = bool(o.get("attn_save_p", True))
+        #   dw_group       adapter gradient products per launch (<= 16)
+        self.dw_group = max(1, min(L.ADW_MAX_ADAPTERS, int(o.get("dw_group", 16))))
         self._build_flat()
         self._pack_frozen()
+        self._build_trainable_operands()
+        self._compose_ev = None  # (event after layer 0, event after everything) of the last compose (refresh_trainable_operands)
         self._relidx: Dict[int, torch.Tensor] = {}
         self._pos_cache: Dict[int, torch.Tensor] = {}  # per-layer position projections of inference forwards (_pos_proj_cached)
         self._no_pos_cache = False  # set while an inference graph is captured: a replay must not depend on state kept outside it
         self.reducer = None  # set by parallel.GradReducer for data-parallel training
-        self._pad_bufs = {}
         self._dyz_pool: Dict[tuple, list] = {}  # [N, K_fold] operands of the folded adapter backward with their padding zeroed once
         self._dyz_shape = None                   # ... of the current batch shape only
         self.params_version = 0  # bumped by FusedAdam.step (which updates the flat buffer through raw pointers)
@@ -112,31 +163,13 @@ class Engine:
         # trainable-weight gradients are off the critical path (nothing downstream in backward reads them): they run on a
         # side HIP stream and fill the tails of the big dX GEMMs; own workspaces so they never race with the main stream
         self.side = torch.cuda.Stream(device=dev)  # (stream priorities were measured: no effect on the interference)
+        self.side_ws = torch.empty(8 << 20, dtype=F32, device=dev)
+        self.side_cs_ws = L.colsum_ws(max(self.H, self.I), dev)
         # the caller-provided aux stream of the GEMM entry points (remainder rows of multi-round problems run there,
         # concurrently with the big tiles; include/fbl.h): one per device, owned by the host side
         if L._AUX.get(dev.index if dev.index is not None else torch.cuda.current_device()) is None:
             L.set_aux_stream(torch.cuda.Stream(device=dev), dev)
-        # Engine options: `model.engine_options` (a dict read ONCE, when the engine is built; the product reads no environment
-        # variable).  Defaults are the shipped configuration; the other values exist for A/B measurements (tools/, tests):
-        #   eager_logits   fill the full [N, V] logits in every forward even when only the loss is consumed (reference-eager)
-        #   side_stream    False = single-stream execution (the per-step composition of the merged adapter rows otherwise runs beside the forward)
-        #   fold_dx        adapter dx folded into the dense dX GEMM;  dw_on_side: generic dW route on the side stream
-        #   fuse_tail      adapter up-projection + block dropout + residual as one epilogue (fbl_adapter_up_resid_fwd)
-        #   merge          dense layer + adapter down-projection as one GEMM;  dw_group: adapter gradient products per launch
-        o = self.opts
-        self.eager_logits = bool(o.get("eager_logits", False))
-        self.side_ws = torch.empty(8 << 20, dtype=F32, device=dev)
-        self.side_cs_ws = L.colsum_ws(max(self.H, self.I), dev)
-        self.use_side_stream = bool(o.get("side_stream", True))
-        self.fold_dx = bool(o.get("fold_dx", True))
-        self.dw_on_side = bool(o.get("dw_on_side", False))
-        #   attn_save_p    False = the attention backward recomputes the probabilities and forms dK by the key-major shear pass
-        #                  instead of reading the ones the training forward saved (157 MB per layer execution at the bench shape,
-        #                  held until the backward)
-        self.attn_save_p = bool(o.get("attn_save_p", True))
-        self.fuse_tail = bool(o.get("fuse_tail", True))
         L.exclude_from_aux(self.side)  # side-stream GEMMs never fork into the aux stream of the main stream's GEMMs
-        self.dw_group = max(1, min(L.ADW_MAX_ADAPTERS, int(o.get("dw_group", 16))))  # adapter gradient products per launch (<= 16)
 
     # ------------------------------------------------------------------ parameter plumbing
     def _build_flat(self):
@@ -185,7 +218,7 @@ class Engine:
         if name.startswith("deberta.encoder.layer."):
             return "layer" + name.split(".")[3]
         if name.startswith("deberta.encoder.conv."):
-            return "layer0" if False else "conv"
+            return "conv"
         if name.startswith("deberta.encoder.LayerNorm"):
             return "relln"
         return "emb"
@@ -209,28 +242,11 @@ class Engine:
         P, H, I = self.P, self.H, self.I
         nL, dev = self.nL, self.dev
         bf = lambda t: t.to(BF16).contiguous()
-        # A dense layer followed by an adapter runs as ONE GEMM against [W ; Wd.W] (fbl_dense_adapter_down_fwd): the
-        # composed rows Wd.W change with every optimizer step and are rebuilt by two batched GEMMs per site type
-        # (refresh_trainable_operands).  For those, the transposed frozen weights of all layers live in one tensor, in
-        # REVERSE layer order (index j = nL-1-layer) -- the order of the adapters in the flat trainable buffer.
-        # (the merged GEMM needs the bottleneck unpadded, A % 64 == 0, and the segment boundary H on a wave's column
-        # range, H % 64 == 0: include/fbl.h; otherwise neither the composed weights nor their per-step rebuild exist)
-        self.merge1 = bool(self.A1) and self.A1 % 64 == 0 and H % 64 == 0 and bool(self.opts.get("merge", True))
-        self.merge2 = bool(self.A2) and self.A2 % 64 == 0 and H % 64 == 0 and bool(self.opts.get("merge", True))
+        # The transposed frozen weights in front of the two adapter sites live in one tensor per site type, in REVERSE layer
+        # order (index j = nL-1-layer) -- the order of the adapters in the flat trainable buffer: the per-step compose of
+        # the merged weights runs over them as strided batches (_build_trainable_operands, _compose_adapter_down)
         self.WoT_rev = torch.empty(nL, H, H, dtype=BF16, device=dev)
         self.WdT_rev = torch.empty(nL, I, H, dtype=BF16, device=dev)
-        if self.merge1:
-            # backward twin of the merged weights: dctx = [dy | dz] . [Wo^T | (Wd.Wo)^T]^T folds the adapter's dx = dy + dz.Wd
-            # into the dense layer's dX GEMM (K = H + A1, padded to an even number of 64-wide K tiles with zero columns)
-            self.Kf1 = _ru(H + self.A1, 128)
-            self.WoF_rev = torch.zeros(nL, H, self.Kf1, dtype=BF16, device=dev)
-            self.WoM_rev = torch.zeros(nL, H + self.A1, H, dtype=BF16, device=dev)
-            self.boM_rev = torch.zeros(nL, H + self.A1, dtype=F32, device=dev)
-            self.bo16_rev = torch.zeros(nL, 1, H, dtype=BF16, device=dev)
-        if self.merge2:
-            self.WdM_rev = torch.zeros(nL, H + self.A2, I, dtype=BF16, device=dev)
-            self.bdM_rev = torch.zeros(nL, H + self.A2, dtype=F32, device=dev)
-            self.bd16_rev = torch.zeros(nL, 1, H, dtype=BF16, device=dev)
         self.Lw = []
         for i in range(self.nL):
             p = f"deberta.encoder.layer.{i}"
@@ -249,18 +265,6 @@ class Engine:
                 Wd=bf(P[p + ".output.dense.weight"]), WdT=self.WdT_rev[j],
                 bd=P[p + ".output.dense.bias"].float().contiguous(),
             )
-            if self.merge1:
-                self.WoM_rev[j, :H].copy_(d["Wo"])
-                self.boM_rev[j, :H].copy_(d["bo"])
-                self.bo16_rev[j, 0].copy_(d["bo"])
-                d["WoM"], d["boM"] = self.WoM_rev[j], self.boM_rev[j]
-                self.WoF_rev[j, :, :H].copy_(self.WoT_rev[j])
-                d["WoF"] = self.WoF_rev[j]
-            if self.merge2:
-                self.WdM_rev[j, :H].copy_(d["Wd"])
-                self.bdM_rev[j, :H].copy_(d["bd"])
-                self.bd16_rev[j, 0].copy_(d["bd"])
-                d["WdM"], d["bdM"] = self.WdM_rev[j], self.bdM_rev[j]
             self.Lw.append(d)
         # [Wq ; Wk]^T of every layer EXECUTION that has a backward, in backward order (the last layer's two enhanced-mask-decoder
         # passes, then layers nL-2 .. 0): the position-table gradients of all of them are projected by one strided-batch GEMM
@@ -290,6 +294,57 @@ class Engine:
             self.Ansb = bf(T)
             self.ans_bias = P["answer_bias"].float().contiguous()
 
+    def _build_trainable_operands(self):
+        """The adapter sites and the video projection: stable views / persistent buffers of every bf16 operand that follows
+        the trainable parameters (refresh_trainable_operands fills them)."""
+        H, nL, dev = self.H, self.nL, self.dev
+        self.sites = [[None, None] for _ in range(nL)]  # per layer: [attention-output adapter, FFN-output adapter] or None
+        self.packs: List[MergedPack] = []
+        for k, (blk, A, K, WT, wkey, bkey) in enumerate(((".attention.output.adapter", self.A1, H, self.WoT_rev, "Wo", "bo"),
+                                                         (".output.adapter", self.A2, self.I, self.WdT_rev, "Wd", "bd"))):
+            if not A:
+                continue
+            Ap = _ru(A, 64)
+            merged = A % 64 == 0 and H % 64 == 0
+            names = [f"deberta.encoder.layer.{i}{blk}" for i in range(nL)]
+            pack = None
+            if merged:
+                # backward twin of the merged weights: dctx = [dy | dz] . [Wo^T | (Wd.Wo)^T]^T folds the adapter's dx = dy + dz.Wd
+                # into the dense layer's dX GEMM (K = H + A1, padded to an even number of 64-wide K tiles with zero columns)
+                WF = torch.zeros(nL, H, _ru(H + A, 128), dtype=BF16, device=dev) if k == 0 else None
+                # Layers nL-1 .. 1 sit at a constant stride in the flat trainable buffer: one strided batch; layer 0 (the conv
+                # LayerNorm sits between it and layer 1) gets its own and goes first
+                ow = [self.offsets[n + ".down.weight"] for n in names]
+                ob = [self.offsets[n + ".down.bias"] for n in names]
+                if nL >= 3 and len({ow[i - 1] - ow[i] for i in range(2, nL)}) == 1 and \
+                        len({ob[i - 1] - ob[i] for i in range(2, nL)}) == 1 and ow[nL - 2] - ow[nL - 1] == ob[nL - 2] - ob[nL - 1] > 0:
+                    groups = [(nL - 1, 1, ow[0], ob[0], A * H), (0, nL - 1, ow[nL - 1], ob[nL - 1], ow[nL - 2] - ow[nL - 1])]
+                else:
+                    groups = [(nL - 1 - i, 1, ow[i], ob[i], A * H) for i in range(nL)]
+                pack = MergedPack(A=A, WT=WT, WM=torch.zeros(nL, H + A, K, dtype=BF16, device=dev),
+                                  bM=torch.zeros(nL, H + A, dtype=F32, device=dev),
+                                  b16=torch.zeros(nL, 1, H, dtype=BF16, device=dev), WF=WF, groups=groups)
+                self.packs.append(pack)
+            for i, n in enumerate(names):
+                j = nL - 1 - i
+                # (Ap != A: the zero-padded copy of up.weight [H, A] lives in a persistent buffer)
+                up = self.Pb[n + ".up.weight"] if Ap == A else torch.zeros(H, Ap, dtype=BF16, device=dev)
+                site = AdapterSite(name=n, A=A, Ap=Ap, down=self.Pb[n + ".down.weight"], up=up, bd=self.P[n + ".down.bias"],
+                                   bu=self.P[n + ".up.bias"], merged=merged, grouped=Ap <= 256 and H % 8 == 0)
+                if merged:
+                    pack.WM[j, :H].copy_(self.Lw[i][wkey])
+                    pack.bM[j, :H].copy_(self.Lw[i][bkey])
+                    pack.b16[j, 0].copy_(self.Lw[i][bkey])
+                    site.WM, site.bM = pack.WM[j], pack.bM[j]
+                    if pack.WF is not None:
+                        pack.WF[j, :, :H].copy_(WT[j])
+                        site.WF = pack.WF[j]
+                self.sites[i][k] = site
+        self.all_sites = [a for pair in self.sites for a in pair if a is not None]
+        if self.F:
+            wv = self.Pb["deberta.embeddings.linear_video.weight"]
+            self.Wv = wv if self.Fp == self.F else torch.zeros(H, self.Fp, dtype=BF16, device=dev)
+
     def relidx(self, S: int) -> torch.Tensor:
         if S not in self._relidx:
             v = rel_index_vector(S, self.cfg.position_buckets, self.cfg.max_rel, self.cfg.att_span)
@@ -318,9 +373,8 @@ class Engine:
         current stream has waited for the side stream that composes them (a captured forward may not wait on events
         recorded outside its capture, so `_compose_ev` is consumed here)."""
         self._refresh_if_stale(False)
-        ev = getattr(self, "_compose_ev", None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev[1])
+        if self._compose_ev is not None:
+            torch.cuda.current_stream().wait_event(self._compose_ev[1])
             self._compose_ev = None
 
     def invalidate_operands(self):
@@ -332,129 +386,77 @@ class Engine:
         """bf16 MFMA operands of the trainable matrices (they change every optimizer step)."""
         self._pos_cache.clear()
         L.cast_bf16(self.flat, self.flat_bf16)
-        H = self.H
-        self.ad = []
-        for i in range(self.nL):
-            p = f"deberta.encoder.layer.{i}"
-            ent = {}
-            for key, blk, A in (("a1", ".attention.output.adapter", self.A1), ("a2", ".output.adapter", self.A2)):
-                if not A:
-                    continue
-                Ap = _ru(A, 64)
-                down = self.Pb[p + blk + ".down.weight"]  # [A,H]
-                up = self.Pb[p + blk + ".up.weight"]  # [H,A]
-                if Ap != A:  # zero-padded copy in a persistent buffer (stable address: captured graphs keep reading it)
-                    upp = self._pad_bufs.get((i, key))
-                    if upp is None:
-                        upp = self._pad_bufs[(i, key)] = torch.zeros(H, Ap, dtype=BF16, device=self.dev)
-                    upp[:, :A] = up
-                    up = upp
-                ent[key] = dict(down=down, up=up, A=A, Ap=Ap, name=p + blk,
-                                bd=self.P[p + blk + ".down.bias"], bu=self.P[p + blk + ".up.bias"])
-            self.ad.append(ent)
+        for a in self.all_sites:
+            if a.Ap != a.A:
+                a.up[:, :a.A] = self.Pb[a.name + ".up.weight"]
+            a.upT = a.downT = None
         # composed rows of the merged dense + down-projection weights: off the critical path, on the side stream (layer 0
         # first -- the forward reaches its merged GEMM after ~0.3 ms -- then all other layers in one strided batch)
-        if self.merge1 or self.merge2:
-            if self.use_side_stream:
-                self.side.wait_stream(torch.cuda.current_stream())  # the bf16 cast of the flat buffer above
-                with torch.cuda.stream(self.side):
-                    self._compose_ev = self._compose_adapter_down(events=True)
-            else:
-                self._compose_adapter_down()
-                self._compose_ev = None
-        if self.F:
-            wv = self.Pb["deberta.embeddings.linear_video.weight"]
-            if self.Fp != self.F:
-                w2 = self._pad_bufs.get("Wv")
-                if w2 is None:
-                    w2 = self._pad_bufs["Wv"] = torch.zeros(H, self.Fp, dtype=BF16, device=self.dev)
-                w2[:, : self.F] = wv
-                wv = w2
-            self.Wv = wv
+        if self.packs:
+            self.side.wait_stream(torch.cuda.current_stream())  # the bf16 cast of the flat buffer above
+            with torch.cuda.stream(self.side):
+                self._compose_ev = self._compose_adapter_down()
+        if self.F and self.Fp != self.F:
+            self.Wv[:, : self.F] = self.Pb["deberta.embeddings.linear_video.weight"]
 
-    def _compose_adapter_down(self, events=False, grad=True):
-        """Rows [H, H+A) of the merged weights / biases: Wd.W and Wd.b + bd for every layer (see _pack_frozen), from the
-        current adapter weights.  Layers nL-1 .. 1 sit at a constant stride in the flat trainable buffer: one strided-batch
-        GEMM each for the matrix and the bias; layer 0 (the conv LayerNorm sits between it and layer 1) gets its own and
-        goes first.  events=True: returns (event after layer 0, event after everything) recorded on the current stream."""
-        H, nL = self.H, self.nL
-        sites = []
-        for on, blk, A, WT, WM, bM, b16, WF in ((self.merge1, ".attention.output.adapter", self.A1, self.WoT_rev,
-                                                 getattr(self, "WoM_rev", None), getattr(self, "boM_rev", None),
-                                                 getattr(self, "bo16_rev", None), getattr(self, "WoF_rev", None)),
-                                                (self.merge2, ".output.adapter", self.A2, self.WdT_rev,
-                                                 getattr(self, "WdM_rev", None), getattr(self, "bdM_rev", None),
-                                                 getattr(self, "bd16_rev", None), None)):
-            if not on:
-                continue
-            ow = [self.offsets[f"deberta.encoder.layer.{i}{blk}.down.weight"] for i in range(nL)]
-            ob = [self.offsets[f"deberta.encoder.layer.{i}{blk}.down.bias"] for i in range(nL)]
-            if nL >= 3 and len({ow[i - 1] - ow[i] for i in range(2, nL)}) == 1 and \
-                    len({ob[i - 1] - ob[i] for i in range(2, nL)}) == 1 and ow[nL - 2] - ow[nL - 1] == ob[nL - 2] - ob[nL - 1] > 0:
-                groups = [(nL - 1, 1, ow[0], ob[0], A * H), (0, nL - 1, ow[nL - 1], ob[nL - 1], ow[nL - 2] - ow[nL - 1])]
-            else:
-                groups = [(nL - 1 - i, 1, ow[i], ob[i], A * H) for i in range(nL)]
-            sites.append((A, WT, WM, bM, b16, groups, WF))
+    def _compose_adapter_down(self):
+        """Rows [H, H+A) of the merged weights / biases: Wd.W and Wd.b + bd for every layer (see MergedPack), from the
+        current adapter weights: one strided-batch GEMM each for the matrix and the bias per group of layers, layer 0 of
+        every site type first.  Returns (event after layer 0, event after everything) recorded on the current stream."""
+        H = self.H
 
-        def run_group(A, WT, WM, bM, b16, grp, WF=None):
-            j0, nb, o_w, o_b, st = grp
+        def run_group(pk: MergedPack, grp):
+            A, (j0, nb, o_w, o_b, st) = pk.A, grp
             wd3 = torch.as_strided(self.flat_bf16, (nb, A, H), (st, H, 1), o_w)
-            L.gemm(wd3, WT[j0:j0 + nb], out_bf16=WM[j0:j0 + nb, H:H + A, :])                # Wd . W
-            if WF is not None and grad:  # (Wd . W)^T next to W^T: the K-extension of the folded backward GEMM
-                L.gemm(WT[j0:j0 + nb], wd3, out_bf16=WF[j0:j0 + nb, :, H:H + A])
+            L.gemm(wd3, pk.WT[j0:j0 + nb], out_bf16=pk.WM[j0:j0 + nb, H:H + A, :])                # Wd . W
+            if pk.WF is not None:  # (Wd . W)^T next to W^T: the K-extension of the folded backward GEMM
+                L.gemm(pk.WT[j0:j0 + nb], wd3, out_bf16=pk.WF[j0:j0 + nb, :, H:H + A])
             bd3 = torch.as_strided(self.flat, (nb, A, 1), (st, 1, 1), o_b)
-            bo3 = torch.as_strided(bM, (nb, A, 1), (bM.stride(0), 1, 1), bM[j0, H:].storage_offset())
-            L.gemm(wd3, b16[j0:j0 + nb], aux=bd3, aux_kind=L.AUX_ADD_F32, out_f32=bo3)      # Wd . b + bd
+            bo3 = torch.as_strided(pk.bM, (nb, A, 1), (pk.bM.stride(0), 1, 1), pk.bM[j0, H:].storage_offset())
+            L.gemm(wd3, pk.b16[j0:j0 + nb], aux=bd3, aux_kind=L.AUX_ADD_F32, out_f32=bo3)        # Wd . b + bd
 
-        for A, WT, WM, bM, b16, groups, WF in sites:  # layer 0 of every site first
-            run_group(A, WT, WM, bM, b16, groups[0], WF)
-        ev0 = ev1 = None
-        if events:
-            ev0 = torch.cuda.Event()
-            ev0.record()
-        for A, WT, WM, bM, b16, groups, WF in sites:
-            for grp in groups[1:]:
-                run_group(A, WT, WM, bM, b16, grp, WF)
-        if events:
-            ev1 = torch.cuda.Event()
-            ev1.record()
-            return ev0, ev1
-        return None
+        for pk in self.packs:
+            run_group(pk, pk.groups[0])
+        ev0 = torch.cuda.Event()
+        ev0.record()
+        for pk in self.packs:
+            for grp in pk.groups[1:]:
+                run_group(pk, grp)
+        ev1 = torch.cuda.Event()
+        ev1.record()
+        return ev0, ev1
 
-    def _adapter_bwd_operands(self, ent):
+    def _adapter_bwd_operands(self, site: AdapterSite):
         """W^T operands for the adapter backward (trainable, so rebuilt after every optimizer step): all adapters of a
         shape are transposed by ONE batched launch straight out of the flat bf16 parameter copy, on first use in a
         step.  Bottlenecks that are not a multiple of 64 take the zero-padded per-adapter path."""
-        if "upT" not in ent:
+        if site.upT is None:
             H = self.H
             groups = {}
-            for e in self.ad:
-                for key in ("a1", "a2"):
-                    if key in e:
-                        groups.setdefault((e[key]["A"], e[key]["Ap"]), []).append(e[key])
-            for (A, Ap), ents in groups.items():
-                upT_all = torch.empty(len(ents), A, H, dtype=BF16, device=self.dev)
-                for i, e in enumerate(ents):
-                    e["upT"] = upT_all[i]  # [A,H] = up.weight[H,A]^T
+            for a in self.all_sites:
+                groups.setdefault((a.A, a.Ap), []).append(a)
+            for (A, Ap), sites in groups.items():
+                upT_all = torch.empty(len(sites), A, H, dtype=BF16, device=self.dev)
+                for i, a in enumerate(sites):
+                    a.upT = upT_all[i]  # [A,H] = up.weight[H,A]^T
                 cache = self._adT_offs.get((A, Ap))
                 if cache is None:
                     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=self.dev)
-                    cache = dict(up_src=i64([self.offsets[e["name"] + ".up.weight"] for e in ents]),
-                                 dn_src=i64([self.offsets[e["name"] + ".down.weight"] for e in ents]),
-                                 dst=i64([i * A * H for i in range(len(ents))]))
+                    cache = dict(up_src=i64([self.offsets[a.name + ".up.weight"] for a in sites]),
+                                 dn_src=i64([self.offsets[a.name + ".down.weight"] for a in sites]),
+                                 dst=i64([i * A * H for i in range(len(sites))]))
                     self._adT_offs[(A, Ap)] = cache
                 L.transpose_batched_bf16(self.flat_bf16, cache["up_src"], upT_all, cache["dst"], H, A)
                 if Ap == A:
-                    dnT_all = torch.empty(len(ents), H, A, dtype=BF16, device=self.dev)
+                    dnT_all = torch.empty(len(sites), H, A, dtype=BF16, device=self.dev)
                     L.transpose_batched_bf16(self.flat_bf16, cache["dn_src"], dnT_all, cache["dst"], A, H)
-                    for i, e in enumerate(ents):
-                        e["downT"] = dnT_all[i]  # [H,A] = down.weight[A,H]^T
+                    for i, a in enumerate(sites):
+                        a.downT = dnT_all[i]  # [H,A] = down.weight[A,H]^T
                 else:  # K of the consuming GEMM must be a multiple of 64: zero-padded columns
-                    for e in ents:
-                        downT = torch.zeros(H, Ap, dtype=BF16, device=self.dev)
-                        downT[:, :A].copy_(self.Pb[e["name"] + ".down.weight"].t())
-                        e["downT"] = downT
-        return ent["upT"], ent["downT"]
+                    for a in sites:
+                        a.downT = torch.zeros(H, Ap, dtype=BF16, device=self.dev)
+                        a.downT[:, :A].copy_(a.down.t())
+        return site.upT, site.downT
 
     # ------------------------------------------------------------------ public entry
     def run(self, input_ids, attention_mask, video, video_mask, labels, mlm, want_hidden, logit_rows=None, want_attn=False):
@@ -506,16 +508,11 @@ class Engine:
         run = Run(B=B, S=S, T=T, Lt=Lt, train=train, save=need_grad, seed_base=self.seed_word_value() if train else 0,
                   p_hid=self.cfg.hidden_dropout_prob if train else 0.0,
                   p_att=self.cfg.attention_probs_dropout_prob if train else 0.0,
-                  p_ad=m.adapter_dropout if train else 0.0)
-        run.mask = mask.view(-1)
-        run.pk = pk
-        run.N = pk.n if pk is not None else B * S
-        run.want_attn = bool(want_attn)
+                  p_ad=m.adapter_dropout if train else 0.0, mask=mask.view(-1), pk=pk, N=pk.n if pk is not None else B * S,
+                  want_attn=bool(want_attn), labels=full_labels, rows=rows_labelled if full_labels is not None else None)
         if want_attn and train and run.p_att > 0:
             raise NotImplementedError("output_attentions=True is served in eval mode (the probabilities of a training forward "
                                       "carry the attention dropout mask, which the fused kernel regenerates instead of storing)")
-        run.labels = full_labels
-        run.rows = rows_labelled if full_labels is not None else None
         if pk is not None and full_labels is not None:  # the head works on packed rows; the labels are looked up on the grid
             run.label_rows = rows_labelled
             run.rows = pk.inv[rows_labelled]
@@ -530,15 +527,10 @@ class Engine:
         with L.seed_word(run.seed_word):
             logits, loss_t = self._forward(run, input_ids.contiguous(), video, use_ans, want_hidden or want_attn)
         Vout = self.n_ans if use_ans else self.V
-        if logit_rows is not None:
+        if logit_rows is not None:  # (an inference call: neither of the loss / autograd branches below applies)
             res = {"logits": logits[:, :Vout], "loss": None, "run": run}
-            if want_hidden:
-                res["hidden_states"] = run.hidden_out
-            if want_attn:
-                res["attentions"] = tuple(run.attn_out)
-            return res
-        res = {"logits": logits.view(B, S, -1)[:, :, :Vout] if logits is not None else None, "loss": None, "run": run}
-        # (packed rows: `logits` is the [B*S, V] grid tensor here too -- allocated in _forward, filled on access)
+        else:  # (packed rows: `logits` is the [B*S, V] grid tensor here too -- allocated in _forward, filled on access)
+            res = {"logits": logits.view(B, S, -1)[:, :, :Vout] if logits is not None else None, "loss": None, "run": run}
         if want_hidden:
             res["hidden_states"] = run.hidden_out
         if want_attn:
@@ -598,69 +590,47 @@ class Engine:
                  out_f32=of, N=N, H=H)
         return Stream(bf16=ob, norm=NormRef(t, stats, g, b, rowmask), plain=of, full=full if tail else None), seed
 
-    def _adapter_fwd(self, run, ent, x_f32, x_bf16, N, z=None, seed=0):
-        """y = x + up(drop(relu(down(x))))  (model/adapter.py:33-45).  The bottleneck z either comes from the merged
-        dense + down-projection GEMM of the caller (z given) or from fbl_adapter_down_fwd; the up-projection is a GEMM
-        with bias + residual epilogue."""
-        A, Ap = ent["A"], ent["Ap"]
-        if z is None:
-            z = torch.zeros(N, Ap, dtype=BF16, device=self.dev) if Ap != A else torch.empty(N, Ap, dtype=BF16, device=self.dev)
-            seed = run.next_seed() if run.p_ad > 0 else 0
-            L.adapter_down_fwd(x_bf16, ent["down"], ent["bd"], z, A=A, p_drop=run.p_ad, seed=seed)  # ReLU + dropout in the epilogue
+    def _adapter_fwd(self, run, site: AdapterSite, x_f32, x_bf16, N):
+        """y = x + up(drop(relu(down(x))))  (model/adapter.py:33-45): fbl_adapter_down_fwd, then the up-projection as a GEMM
+        with bias + residual epilogue.  Returns (y, bottleneck z, dropout seed)."""
+        A, Ap = site.A, site.Ap
+        z = torch.zeros(N, Ap, dtype=BF16, device=self.dev) if Ap != A else torch.empty(N, Ap, dtype=BF16, device=self.dev)
+        seed = run.next_seed() if run.p_ad > 0 else 0
+        L.adapter_down_fwd(x_bf16, site.down, site.bd, z, A=A, p_drop=run.p_ad, seed=seed)  # ReLU + dropout in the epilogue
         y = torch.empty(N, self.H, dtype=F32, device=self.dev)
-        L.gemm(z, ent["up"], bias=ent["bu"], aux=x_f32, aux_kind=L.AUX_ADD_F32, out_f32=y)
+        L.gemm(z, site.up, bias=site.bu, aux=x_f32, aux_kind=L.AUX_ADD_F32, out_f32=y)
         return y, z, seed
 
-    def _dense_adapter(self, run, li, x_bf16, W, wkey, bkey, ent, A, merged, N):
-        """dense -> adapter (model/deberta.py:255-257 / :329-331): returns (y fp32 = adapter output, dense output bf16, z,
-        dropout seed).  Merged form: one GEMM gives the dense output and the adapter bottleneck."""
-        H, dev = self.H, self.dev
-        o32 = torch.empty(N, H, dtype=F32, device=dev)
-        # the bf16 copy of the dense output is the adapter's GEMM operand: with the merged GEMM (the bottleneck comes out
-        # of the same launch) only the backward reads it -- an inference forward does not write it (26 MB per site)
-        need_ob = run.save or ent is None or not (merged and ent["Ap"] == A)
-        ob = torch.empty(N, H, dtype=BF16, device=dev) if need_ob else None
-        if ent is None:
-            L.gemm(x_bf16, W[wkey], bias=W[bkey], out_f32=o32, out_bf16=ob)
-            return o32, ob, None, 0
-        if merged and ent["Ap"] == A:
-            ev = getattr(self, "_compose_ev", None)
-            if ev is not None:  # the composed rows of this layer must be there (layer 0: first event, others: second)
-                torch.cuda.current_stream().wait_event(ev[0] if li == 0 else ev[1])
-            z = torch.empty(N, A, dtype=BF16, device=dev)
-            seed = run.next_seed() if run.p_ad > 0 else 0
-            L.dense_adapter_down_fwd(x_bf16, W[wkey + "M"], W[bkey + "M"], H, z, y_f32=o32, y_bf16=ob, p_drop=run.p_ad, seed=seed)
-            y, z, seed = self._adapter_fwd(run, ent, o32, ob, N, z=z, seed=seed)
-        else:
-            L.gemm(x_bf16, W[wkey], bias=W[bkey], out_f32=o32, out_bf16=ob)
-            y, z, seed = self._adapter_fwd(run, ent, o32, ob, N)
-        return y, ob, z, seed
-
-    def _dense_adapter_ln(self, run, li, x_bf16, W, wkey, bkey, ent, A, merged, N, ln_name, resid: Stream, tail=0):
+    def _dense_adapter_ln(self, run, li, x_bf16, W, bias, site: Optional[AdapterSite], N, ln_name, resid: Stream, tail=0):
         """dense -> adapter -> dropout -> LayerNorm(. + resid)  (model/deberta.py:254-260 / 328-334).  Returns (output
         Stream, dense output bf16, z, adapter seed, LayerNorm-dropout seed).  With a merged adapter site the block is three
         launches -- merged dense + down-projection GEMM (bf16 y, z), up-projection GEMM whose epilogue adds the adapter
         input, applies the block's dropout and adds the residual (writes the pre-norm tensor t once), LayerNorm statistics
-        + bf16 operand -- and neither the fp32 dense output nor the fp32 adapter output exist in HBM."""
+        + bf16 operand -- and neither the fp32 dense output nor the fp32 adapter output exist in HBM.  Any other site: the
+        plain dense GEMM (W, bias), the adapter if there is one, the full LayerNorm kernel."""
         H, dev = self.H, self.dev
-        if not (self.fuse_tail and ent is not None and merged and ent["Ap"] == A):
-            y, ob, z, seed_ad = self._dense_adapter(run, li, x_bf16, W, wkey, bkey, ent, A, merged, N)
+        ob = torch.empty(N, H, dtype=BF16, device=dev)  # bf16 dense output: the adapter's GEMM operand / saved for its backward
+        if site is None or not site.merged:
+            y = torch.empty(N, H, dtype=F32, device=dev)
+            L.gemm(x_bf16, W, bias=bias, out_f32=y, out_bf16=ob)
+            z, seed_ad = None, 0
+            if site is not None:
+                y, z, seed_ad = self._adapter_fwd(run, site, y, ob, N)
             out, seed_ln = self._ln(run, ln_name, y=y, resid=resid, N=N, p_drop=run.p_hid, tail=tail)
             return out, ob, z, seed_ad, seed_ln
-        ev = getattr(self, "_compose_ev", None)
-        if ev is not None:  # the composed rows of this layer must be there (layer 0: first event, others: second)
-            torch.cuda.current_stream().wait_event(ev[0] if li == 0 else ev[1])
-        ob = torch.empty(N, H, dtype=BF16, device=dev)
+        if self._compose_ev is not None:  # the composed rows of this layer must be there (layer 0: first event, others: second)
+            torch.cuda.current_stream().wait_event(self._compose_ev[0 if li == 0 else 1])
+        A = site.A
         z = torch.empty(N, A, dtype=BF16, device=dev)
         seed_ad = run.next_seed() if run.p_ad > 0 else 0
-        L.dense_adapter_down_fwd(x_bf16, W[wkey + "M"], W[bkey + "M"], H, z, y_bf16=ob, p_drop=run.p_ad, seed=seed_ad)
+        L.dense_adapter_down_fwd(x_bf16, site.WM, site.bM, H, z, y_bf16=ob, p_drop=run.p_ad, seed=seed_ad)
         g, b = self.P[ln_name + ".weight"], self.P[ln_name + ".bias"]
         t = torch.empty(N, H, dtype=F32, device=dev)
         stats = torch.empty(N, 2, dtype=F32, device=dev)
         full = torch.empty(N + tail, H, dtype=BF16, device=dev)
         seed_ln = run.next_seed() if run.p_hid > 0 else 0
         r_norm = resid.norm.as_args() if resid.norm is not None else None
-        L.adapter_up_resid_fwd(z, ent["up"], ent["bu"], ob, t, A=A, p_drop=run.p_hid, seed=seed_ln,
+        L.adapter_up_resid_fwd(z, site.up, site.bu, ob, t, A=A, p_drop=run.p_hid, seed=seed_ln,
                                r_plain=resid.plain if r_norm is None else None, r_norm=r_norm)
         L.ln_fwd(y=t, gamma=g, beta=b, eps=self.cfg.layer_norm_eps, out_stats=stats, out_bf16=full[:N], N=N, H=H)
         return (Stream(bf16=full[:N], norm=NormRef(t, stats, g, b, None), full=full if tail else None), ob, z, seed_ad,
@@ -706,7 +676,7 @@ class Engine:
         infer = not run.save and run.p_hid == 0
         pqk_c = (self._pos_proj_cached(li, W, Rb)
                  if infer and getattr(self.m, "_weights_frozen", 0) > 0 and not self._no_pos_cache else None)
-        reuse = infer and q is not None and getattr(run, "emd_qkv", None) is not None
+        reuse = infer and q is not None and run.emd_qkv is not None
         if reuse:
             qkv = run.emd_qkv
             if pqk_c is None:
@@ -745,7 +715,7 @@ class Engine:
                           seed=sv.seed_att, klen=run.klen, border=run.border, lin=self.lin_span,
                           row0=run.pk.row0 if run.pk is not None else None, psave=psave, msave=msave)
         sv.psave, sv.msave = psave, msave
-        if getattr(run, "want_attn", False) and q is None:
+        if run.want_attn and q is None:
             # output_attentions=True: the encoder layers' probabilities (model/deberta.py:544-560; the enhanced-mask-decoder
             # passes are called with return_att=False, :1395-1408), materialised by a plain kernel from the stored lse
             probs = torch.empty(B, nh, S, S, dtype=F32, device=dev)
@@ -753,19 +723,17 @@ class Engine:
                                 1.0 / math.sqrt(64 * 3), probs, B, S, nh)
             run.attn_out.append(probs)
         # attention output: dense -> adapter -> dropout -> LN(. + residual)   (:254-260)
-        ad = self.ad[li]
+        a1, a2 = self.sites[li]
         p = f"deberta.encoder.layer.{li}"
         a, ob, z1, sv.seed_ad1, sv.seed_ln1 = self._dense_adapter_ln(
-            run, li, ctx, W, "Wo", "bo", ad.get("a1"), self.A1, self.merge1, N, p + ".attention.output.LayerNorm",
-            resid=(q if q is not None else kv))
+            run, li, ctx, W["Wo"], W["bo"], a1, N, p + ".attention.output.LayerNorm", resid=(q if q is not None else kv))
         # FFN: gelu(dense) -> dense -> adapter -> dropout -> LN(. + a)          (:310-313, :328-334)
         h = torch.empty(N, I, dtype=BF16, device=dev)
         hpre = torch.empty(N, I, dtype=BF16, device=dev) if run.save else None
         # training: the epilogue stores gelu'(pre) (bf16) next to gelu(pre) so the backward epilogue is a plain multiply
         L.gemm(a.bf16, W["Wi"], bias=W["bi"], act=L.ACT_GELU_GRAD if run.save else L.ACT_GELU, out_bf16=h, out_pre=hpre)
         out, fb, z2, sv.seed_ad2, sv.seed_ln2 = self._dense_adapter_ln(
-            run, li, h, W, "Wd", "bd", ad.get("a2"), self.A2, self.merge2, N, p + ".output.LayerNorm",
-            resid=Stream(bf16=a.bf16, norm=a.norm), tail=self.span2)
+            run, li, h, W["Wd"], W["bd"], a2, N, p + ".output.LayerNorm", resid=Stream(bf16=a.bf16, norm=a.norm), tail=self.span2)
         if run.save:
             sv.qkv, sv.pqk, sv.ctx, sv.lse = qkv[:N], qkv[N:, : 2 * H], ctx, lse  # (run.save: never the inference shortcuts)
             sv.ob, sv.z1, sv.ln1 = ob, z1, a.norm
@@ -776,9 +744,7 @@ class Engine:
     def _forward(self, run, input_ids, video, use_ans, want_hidden):
         cfg, H, dev = self.cfg, self.H, self.dev
         B, S, T, Lt = run.B, run.S, run.T, run.Lt
-        pk = getattr(run, "pk", None)
-        if not run.N:
-            run.N = B * S
+        pk = run.pk
         N = run.N
         run.mask_i32 = run.mask  # [B*S]: the attention kernels index the mask on the padded grid
         run.rowmask = run.mask if pk is None else run.mask[pk.sel].contiguous()  # per activation row
@@ -852,7 +818,7 @@ class Engine:
                                        .view(B, S, H) for s in hs)
         # ---- MLM head (:1544-1558): LN(gelu(dense(x))) . table^T + bias
         hin = q.bf16
-        rows_only = getattr(run, "logit_rows", None)
+        rows_only = run.logit_rows
         # an inference forward that is only asked for the loss (evaluate, main.py:139) runs the head's dense + GELU +
         # LayerNorm on the labelled rows only, like the vocabulary GEMM below; fill_logits redoes it on every row if the
         # logits are read after all
@@ -893,7 +859,7 @@ class Engine:
                     L.gather_rows_bf16(hl.bf16, run.rows_i32, hrows)
                 lc = torch.empty(R, ldv, dtype=F32, device=dev)
                 L.gemm(hrows, table, bias=bias, out_f32=lc, N=Vout)
-                lab_rows = getattr(run, "label_rows", None)  # (packed rows: `rows` are activation rows, the labels live on the grid)
+                lab_rows = run.label_rows  # (packed rows: `rows` are activation rows, the labels live on the grid)
                 run.labels_c = run.labels[rows if lab_rows is None else lab_rows].contiguous()
                 run.row_lse = torch.empty(R, dtype=F32, device=dev)
                 L.ce_fwd(lc, run.labels_c, Vout, run.row_lse, run.loss_acc)
@@ -912,13 +878,13 @@ class Engine:
     def fill_logits(self, run):
         """Full [N, V] logits of a forward that only computed the labelled rows (see _forward); idempotent.  Writes into
         the storage of the tensor already handed out (and already wired into the autograd node), on the current stream."""
-        if getattr(run, "logits_pending", False):
+        if run.logits_pending:
             run.logits_pending = False
-            hin_all = getattr(run, "head_in_all", None)
+            hin_all = run.head_in_all
             if hin_all is not None:  # the forward ran the head on the labelled rows only: now on every row
                 _, hl = self._head_stage(run, hin_all, hin_all.shape[0])
                 run.head_ln_bf16, run.head_in_all = hl.bf16, None
-            pk = getattr(run, "pk", None)
+            pk = run.pk
             if pk is None:
                 L.gemm(run.head_ln_bf16, run.head_table, bias=run.head_bias, out_f32=run.logits, N=run.Vout)
             else:  # packed rows: grid positions without a row read as zero; the others arrive in slabs of 1024 rows
@@ -959,7 +925,7 @@ class Engine:
         """ConvLayer (:395-419): LN(l0 + gelu(drop(mask * conv1d_k3(emb)))) * mask, conv as a K=3H GEMM on an im2col."""
         B, S, H, dev = run.B, run.S, self.H, self.dev
         N = run.N
-        pk = getattr(run, "pk", None)
+        pk = run.pk
         if pk is None:
             col = torch.empty(N, 3 * H, dtype=BF16, device=dev)
             L.im2col3(emb.bf16, col, B, S, H)
@@ -995,14 +961,14 @@ class Engine:
             return dt, dyb, dt_full
         return dt, dyb
 
-    def _adapter_bwd(self, run, ent, dyb, z, xin_b, seed, dz_out=None, pooled=None):
+    def _adapter_bwd(self, run, site: AdapterSite, dyb, z, xin_b, seed, dz_out=None, pooled=None):
         """Backward of _adapter_fwd.  dyb: grad of the adapter output (bf16 [N,H]); returns grad of its input (bf16).
         dz_out: the caller folds dx = dy + dz.Wd into the next GEMM ([dy | dz] operand, _layer_bwd): dz is written there
         (a column slice of that operand), no dx is formed and None is returned."""
         N, H = dyb.shape
-        A, Ap = ent["A"], ent["Ap"]
+        A, Ap = site.A, site.Ap
         dev = self.dev
-        upT, downT = self._adapter_bwd_operands(ent)
+        upT, downT = self._adapter_bwd_operands(site)
         if dz_out is not None:
             dz = dz_out
         else:
@@ -1014,9 +980,9 @@ class Engine:
             dx = torch.empty(N, H, dtype=BF16, device=dev)
             L.gemm(dz, downT, aux=dyb, aux_kind=L.AUX_ADD_BF16, out_bf16=dx)
         sk = max(2, min(16, N // 512))
-        nm = ent["name"]
+        nm = site.name
 
-        if Ap <= 256 and H % 8 == 0 and not self.dw_on_side:
+        if site.grouped:
             # dWu += dy^T z, dWd += dz^T x, dbd += colsum(dz) are NOT launched here: one adapter alone has 48 output tiles.
             # The operands are parked until `dw_group` adapters are pending and go through ONE launch
             # (fbl_adapter_bwd_dw: every tile walks all rows, no split-K round trip) on the MAIN stream -- its workgroups live
@@ -1026,27 +992,22 @@ class Engine:
             run.dw_count += 1
             return dx
 
-        def dw_work(ws, cs_ws):  # generic route, launched right away: bottlenecks wider than 256 (or engine_options dw_on_side)
-            L.gemm_tn_acc(dyb, z, self.G[nm + ".up.weight"], ws, N=A, splitk=sk)      # dWu[H,A] += dy^T z
-            L.gemm_tn_acc(dz, xin_b, self.G[nm + ".down.weight"], ws, M=A, splitk=sk)  # dWd[A,H] += dz^T x
-            L.colsum(dz, self.G[nm + ".down.bias"], cs_ws, cols=A)
-
-        if self.use_side_stream:
-            main = torch.cuda.current_stream()
-            self.side.wait_stream(main)  # inputs (dyb, z, dz, xin_b) are ready once main reaches this point
-            with torch.cuda.stream(self.side):
-                dw_work(self.side_ws, self.side_cs_ws)
-            if not torch.cuda.is_current_stream_capturing():
-                for t in (dyb, z, dz, xin_b):
-                    t.record_stream(self.side)  # keep the allocator from recycling them before the side stream is done
-            else:  # (inside a capture: referenced for the life of the captured step instead, see _pos_grad_async)
-                run.__dict__.setdefault("_pos_keep", []).extend((dyb, z, dz, xin_b))
-            run.side_used = True
-            if self.reducer is not None:  # what a data-parallel bucket has to wait for: the dW work queued so far
-                run.dw_event = torch.cuda.Event()
-                run.dw_event.record(self.side)
-        else:
-            dw_work(self.sk_ws, self._cs_ws)
+        # Bottlenecks wider than 256: the generic route, launched right away on the side stream (nothing downstream in
+        # backward reads the weight gradients) with its own workspaces
+        self.side.wait_stream(torch.cuda.current_stream())  # inputs (dyb, z, dz, xin_b) are ready once main reaches this point
+        with torch.cuda.stream(self.side):
+            L.gemm_tn_acc(dyb, z, self.G[nm + ".up.weight"], self.side_ws, N=A, splitk=sk)      # dWu[H,A] += dy^T z
+            L.gemm_tn_acc(dz, xin_b, self.G[nm + ".down.weight"], self.side_ws, M=A, splitk=sk)  # dWd[A,H] += dz^T x
+            L.colsum(dz, self.G[nm + ".down.bias"], self.side_cs_ws, cols=A)
+        if not torch.cuda.is_current_stream_capturing():
+            for t in (dyb, z, dz, xin_b):
+                t.record_stream(self.side)  # keep the allocator from recycling them before the side stream is done
+        else:  # (inside a capture: referenced for the life of the captured step instead)
+            run._pos_keep.extend((dyb, z, dz, xin_b))
+        run.side_used = True
+        if self.reducer is not None:  # what a data-parallel bucket has to wait for: the dW work queued so far
+            run.dw_event = torch.cuda.Event()
+            run.dw_event.record(self.side)
         return dx
 
     def _dw_flush(self, run, red=None, force=False):
@@ -1088,55 +1049,54 @@ class Engine:
         """Backward of one layer execution.  dout: fp32 grad of its output.  Returns (dx, None) for ordinary encoder layers (one
         input stream) and (dq_in fp32, [dK | dV] bf16 operand of the key/value-stream gradient) for the decoder form."""
         li = sv.li
-        W, ad = self.Lw[li], self.ad[li]
+        W, (a1, a2) = self.Lw[li], self.sites[li]
         H, I, dev = self.H, self.I, self.dev
         N = dout.shape[0]
         p = f"deberta.encoder.layer.{li}"
         dt2, dy2 = self._ln_bwd(p + ".output.LayerNorm", dout, sv.ln2, run.p_hid, sv.seed_ln2,
-                                dysum=self.G[ad["a2"]["name"] + ".up.bias"] if "a2" in ad else None)
+                                dysum=self.G[a2.name + ".up.bias"] if a2 is not None else None)
         df = dy2
-        if "a2" in ad:
-            df = self._adapter_bwd(run, ad["a2"], dy2, sv.z2, sv.fb, sv.seed_ad2)
+        if a2 is not None:
+            df = self._adapter_bwd(run, a2, dy2, sv.z2, sv.fb, sv.seed_ad2)
         dh = torch.empty(N, I, dtype=BF16, device=dev)
         L.gemm(df, W["WdT"], aux=sv.hpre, aux_kind=L.AUX_MUL_BF16, out_bf16=dh)  # sv.hpre holds gelu'(pre)
         da = torch.empty(N, H, dtype=F32, device=dev)
         L.gemm(dh, W["WiT"], aux=dt2, aux_kind=L.AUX_ADD_F32, out_f32=da)
         del dh
         dctx = torch.empty(N, H, dtype=BF16, device=dev)
-        fold = "a1" in ad and self.fold_dx and "WoF" in W and ad["a1"]["Ap"] == ad["a1"]["A"]
-        if fold:
+        if a1 is not None and a1.merged:
             # dctx = dx . Wo with dx = dy + dz . Wd  ==  [dy | dz] . [Wo^T | (Wd.Wo)^T]^T: LayerNorm backward and the dz GEMM
             # write the two column blocks of ONE operand and the dense dX GEMM runs with K = H + A (+ zero padding) -- the
             # K = A GEMM that formed dx, its 26 MB output and its re-read are gone (25 us per layer execution)
-            A1 = ad["a1"]["A"]
+            A1, Kf = a1.A, a1.WF.shape[1]
             # The K padding columns only have to hold finite values (their weight columns are zero): buffers come from a small
             # pool whose padding was zeroed ONCE -- nobody writes those columns -- instead of a strided fill per layer execution
             # (25 launches a step).  A buffer returns to the pool when the parked gradient products that read its [dy | dz]
             # blocks have been enqueued (_dw_flush).  Captured steps and the immediate-launch route allocate as before.
             pooled = None
-            can_pool = (not torch.cuda.is_current_stream_capturing() and ad["a1"]["Ap"] <= 256 and H % 8 == 0 and not self.dw_on_side)
-            if can_pool and self._dyz_shape != (N, self.Kf1):  # a new batch shape (text padded to the longest sample): one pool, of
+            can_pool = not torch.cuda.is_current_stream_capturing() and a1.grouped
+            if can_pool and self._dyz_shape != (N, Kf):  # a new batch shape (text padded to the longest sample): one pool, of
                 self._dyz_pool.clear()                           # the current shape only -- never one per shape seen
-                self._dyz_shape = (N, self.Kf1)
-            free = self._dyz_pool.get((N, self.Kf1)) if can_pool else None
+                self._dyz_shape = (N, Kf)
+            free = self._dyz_pool.get((N, Kf)) if can_pool else None
             if free:
                 dyz = pooled = free.pop()
             elif can_pool:
-                dyz = pooled = torch.zeros(N, self.Kf1, dtype=BF16, device=dev)
+                dyz = pooled = torch.zeros(N, Kf, dtype=BF16, device=dev)
             else:
-                dyz = torch.empty(N, self.Kf1, dtype=BF16, device=dev)
-                if self.Kf1 > H + A1:
+                dyz = torch.empty(N, Kf, dtype=BF16, device=dev)
+                if Kf > H + A1:
                     dyz[:, H + A1:].zero_()  # finite values under the zero weight columns
             dt1, dy1 = self._ln_bwd(p + ".attention.output.LayerNorm", da, sv.ln1, run.p_hid, sv.seed_ln1,
-                                    dysum=self.G[ad["a1"]["name"] + ".up.bias"], dy_out=dyz[:, :H])
-            self._adapter_bwd(run, ad["a1"], dy1, sv.z1, sv.ob, sv.seed_ad1, dz_out=dyz[:, H:H + A1], pooled=pooled)
-            L.gemm(dyz, W["WoF"], out_bf16=dctx)
+                                    dysum=self.G[a1.name + ".up.bias"], dy_out=dyz[:, :H])
+            self._adapter_bwd(run, a1, dy1, sv.z1, sv.ob, sv.seed_ad1, dz_out=dyz[:, H:H + A1], pooled=pooled)
+            L.gemm(dyz, a1.WF, out_bf16=dctx)
         else:
             dt1, dy1 = self._ln_bwd(p + ".attention.output.LayerNorm", da, sv.ln1, run.p_hid, sv.seed_ln1,
-                                    dysum=self.G[ad["a1"]["name"] + ".up.bias"] if "a1" in ad else None)
+                                    dysum=self.G[a1.name + ".up.bias"] if a1 is not None else None)
             do = dy1
-            if "a1" in ad:
-                do = self._adapter_bwd(run, ad["a1"], dy1, sv.z1, sv.ob, sv.seed_ad1)
+            if a1 is not None:
+                do = self._adapter_bwd(run, a1, dy1, sv.z1, sv.ob, sv.seed_ad1)
             L.gemm(do, W["WoT"], out_bf16=dctx)
         dqkv = self._attn_bwd(run, sv, dctx)
         if not sv.emd:
@@ -1163,13 +1123,9 @@ class Engine:
         # The position-table gradients of this execution (dPK = G1^T.Q, dPQ = G2^T.K) are NOT formed here: its dS / dS^T and
         # q / k go on the per-step lists, and one chain at the END of backward handles all executions
         # (attn_bwd.pos_table_grads_batched).  ft_ln=False: nothing trainable sits behind the position tables, nothing is kept.
-        pc = getattr(run, "pos_chain", None)
         st = disent_attn_bwd(self, run, sv, dctx, dqkv, None, defer_pos=True)
-        if pc is not None:
-            pc["seeds"].append(sv.seed_pos)
-            pc["n"] += 1
-            pc["X1"].append(st["dS"]); pc["X2"].append(st["dST"]); pc["Yq"].append(st["q"]); pc["Yk"].append(st["k"])
-            pc["klen"], pc["row0"] = st["klen"], st["row0"]
+        if run.pos_chain is not None:
+            run.pos_chain.add(st, sv.seed_pos)
         return dqkv
 
     def _head_bwd(self, run, rows, dlog, dq, all_rows=False):
@@ -1208,14 +1164,14 @@ class Engine:
         the conditional zero fill of attach_grads)."""
         if not run.save:
             raise RuntimeError("forward was run without gradient bookkeeping")
-        with L.seed_word(getattr(run, "seed_word", None)):
+        with L.seed_word(run.seed_word):
             return self._backward(run, gloss, glogits, attach)
 
     def _backward(self, run, gloss, glogits, attach):
         cfg, H, dev = self.cfg, self.H, self.dev
         B, S, T = run.B, run.S, run.T
         N = run.N
-        pk = getattr(run, "pk", None)
+        pk = run.pk
         if attach:
             self.attach_grads()
         reducer = self.reducer
@@ -1256,7 +1212,7 @@ class Engine:
         if "deberta.encoder.LayerNorm.weight" in self.G:
             from .attn_bwd import pos_chain_buffers
 
-            run.pos_chain = pos_chain_buffers(self, run, len(run.layers))
+            run.pos_chain = pos_chain_buffers(self, run)
         # ---- EMD: two executions of the last layer, newest first
         layers = run.layers
         dkv_ops = []
@@ -1293,7 +1249,7 @@ class Engine:
                 dx, _ = self._layer_bwd(run, sv, dx)
             stage_done(f"layer{sv.li}")
         self._dw_flush(run, red, force=True)
-        if getattr(run, "side_used", False):
+        if run.side_used:
             torch.cuda.current_stream().wait_stream(self.side)  # all adapter dW/db are in the flat grad buffer
         # ---- relative-position LayerNorm (receives grads from every layer execution)
         rn = run.rel_norm
@@ -1358,9 +1314,8 @@ class _Ready:
         self.eng, self.run, self.reducer = eng, run, reducer
 
     def ready(self, key):
-        ev = getattr(self.run, "dw_event", None)
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
+        if self.run.dw_event is not None:
+            torch.cuda.current_stream().wait_event(self.run.dw_event)
         self.reducer.ready(key)
 
     def finish(self):
@@ -1394,6 +1349,7 @@ class LayerSave:
 
 @dataclass
 class Run:
+    """The state of one step (one forward and its backward), of either engine: everything a stage leaves for a later one."""
     B: int
     S: int
     T: int
@@ -1404,18 +1360,61 @@ class Run:
     p_hid: float
     p_att: float
     p_ad: float
-    layers: List[LayerSave] = field(default_factory=list)
-    _site: int = 0
-    mask: torch.Tensor = None
-    labels: torch.Tensor = None
-    hidden_out: tuple = None
-    seed_word: Optional[torch.Tensor] = None  # device word added to every dropout seed of this pass (see Engine.run)
-    want_attn: bool = False
-    attn_out: list = field(default_factory=list)
-    seed_emb: int = 0
-    seed_conv: int = 0
-    pk: Optional["Packing"] = None  # packed-row layout of this pass (model.packed_rows) or None: the padded [B, S] grid
-    N: int = 0                      # activation rows: B*S, or pk.n
+    # ---- inputs (Engine.run / BertEngine.run / train_graph)
+    mask: torch.Tensor = None                      # int32 [B*S]: video mask | attention mask
+    labels: torch.Tensor = None                    # int64 [B*S] on the padded grid (-100: no label), or None
+    rows: torch.Tensor = None                      # int64: the labelled activation rows
+    label_rows: Optional[torch.Tensor] = None      # packed rows only: the same rows on the padded grid (where `labels` live)
+    logit_rows: Optional[torch.Tensor] = None      # int32: inference on these activation rows only
+    want_attn: bool = False                        # output_attentions=True
+    seed_word: Optional[torch.Tensor] = None       # device word added to every dropout seed of this pass (see Engine.run)
+    pk: Optional["Packing"] = None                 # packed-row layout of this pass (model.packed_rows) or None: the padded [B, S] grid
+    N: int = 0                                     # activation rows: B*S, or pk.n
+    _site: int = 0                                 # dropout sites drawn so far (next_seed)
+    # ---- forward, before the layers
+    mask_i32: torch.Tensor = None                  # [B*S]: the mask as the attention kernels index it (padded grid)
+    rowmask: torch.Tensor = None                   # int32 [N]: the mask per activation row
+    mask_f: torch.Tensor = None                    # fp32 [N]: rowmask as a GEMM row scale
+    klen: torch.Tensor = None                      # int32 [B]: last valid position + 1
+    border: torch.Tensor = None                    # int32 [B]: samples longest first (dispatch order of the attention kernels)
+    video_bf16: torch.Tensor = None                # bf16 [B*T, Fp]: operand of linear_video, kept for its weight gradient
+    emb_norm: NormRef = None                       # embedding LayerNorm
+    seed_emb: int = 0                              # dropout behind it
+    rel_norm: NormRef = None                       # encoder.LayerNorm over the relative-position table
+    R32: Optional[torch.Tensor] = None             # fp32 [2*span, H]: that table, materialised for its dropout (training)
+    # ---- layers
+    layers: list = field(default_factory=list)     # LayerSave / BertLayerSave per execution that has a backward
+    emd_qkv: Optional[torch.Tensor] = None         # inference: Q|K|V of the first decoder pass, reused by the second
+    attn_out: list = field(default_factory=list)   # want_attn: fp32 [B, nh, S, S] probabilities per encoder layer
+    hidden_out: tuple = None                       # want_hidden: fp32 [B, S, H] per layer
+    seed_conv: int = 0                             # ConvLayer: dropout seed, conv output c, LayerNorm
+    conv_c: torch.Tensor = None
+    conv_norm: NormRef = None
+    # ---- head
+    head_in_all: Optional[torch.Tensor] = None     # bf16 [N, H] head input when the forward ran the head on the labelled rows only
+    head_pre: torch.Tensor = None                  # fp32: dense output in front of the GELU
+    head_norm: NormRef = None                      # head LayerNorm
+    head_ln_bf16: torch.Tensor = None              # ... its bf16 output: operand of the vocabulary GEMM
+    head_table: torch.Tensor = None                # bf16 [Vout, H], fp32 [Vout]: vocabulary (or answer) table and bias
+    head_bias: torch.Tensor = None
+    Vout: int = 0                                  # logit columns; ldv: their padded leading dimension
+    ldv: int = 0
+    use_ans: bool = False                          # BertEngine: the answer table is the head's table
+    rows_i32: torch.Tensor = None                  # `rows` as int32
+    labels_c: torch.Tensor = None                  # int64 [R]: labels of the labelled rows
+    logits_c: torch.Tensor = None                  # fp32 [R, ldv]: their logits, row_lse [R]: their log-sum-exp
+    row_lse: torch.Tensor = None
+    loss_acc: torch.Tensor = None                  # fp32 [2]: (sum of row losses, labelled rows)
+    logits: torch.Tensor = None                    # fp32 [B*S or rows, ldv]: the tensor handed out
+    logits_pending: bool = False                   # ... not filled yet (fill_logits does it on first access)
+    # ---- backward
+    dw_pending: list = field(default_factory=list)     # parked adapter-gradient products (_adapter_bwd / _dw_flush)
+    dw_ready_keys: list = field(default_factory=list)  # finished stages whose buckets wait for a parked product
+    dw_count: int = 0                              # products parked so far
+    side_used: bool = False                        # the side stream holds weight-gradient work of this pass
+    dw_event: Optional[torch.cuda.Event] = None    # ... recorded behind the latest of it (data-parallel buckets wait for it)
+    _pos_keep: list = field(default_factory=list)  # captured steps: tensors the side stream reads, referenced for the step's life
+    pos_chain: Optional["PosChain"] = None         # attn_bwd.PosChain: what the position-table gradients collect per execution
 
     def __post_init__(self):
         if not self.N:
@@ -1440,7 +1439,6 @@ class _StepFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss, glogits):
         eng, run = ctx.engine, ctx.run
-        if gloss is None and glogits is None:
-            return (None, None, None, None) + tuple(None for _ in eng.order)
-        eng.backward(run, gloss, glogits)
+        if gloss is not None or glogits is not None:
+            eng.backward(run, gloss, glogits)
         return (None, None, None, None) + tuple(None for _ in eng.order)

@@ -214,7 +214,7 @@ class BertForMaskedLM(nn.Module):
         out = MaskedLMOutput(loss=res["loss"], logits=res["logits"], hidden_states=res.get("hidden_states"), attentions=None)
         run = res["run"]
         out.__dict__["_run"] = run
-        if getattr(run, "logits_pending", False):
+        if run.logits_pending:
             out.__dict__["_fill"] = lambda: eng.fill_logits(run)
         if return_dict is False:
             return tuple(v for v in (out["loss"], out["logits"], out["hidden_states"]) if v is not None)

@@ -501,7 +501,7 @@ class DebertaV2ForMaskedLM(nn.Module):
                              attentions=res.get("attentions"))
         run = res.get("run")
         out.__dict__["_run"] = run  # (tests read the saved bottleneck activations through this)
-        if run is not None and getattr(run, "logits_pending", False):
+        if run is not None and run.logits_pending:
             out.__dict__["_fill"] = lambda: eng.fill_logits(run)
         if return_dict is False:
             return tuple(v for v in (out["loss"], out["logits"], out["hidden_states"], out["attentions"]) if v is not None)

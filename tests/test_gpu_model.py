@@ -649,16 +649,24 @@ def test_training_trajectory_follows_the_oracle_over_optimizer_steps():
     assert torch.equal(m.get_param(frozen).float().cpu(), P0[frozen])
 
 
-@pytest.mark.parametrize("ds_attn,ds_ff,ft_ln", [(0, 0, True), (8, 8, False), (0, 8, True), (8, 0, False)],
-                         ids=["no-adapters", "ft_ln-off", "ffn-adapter-only", "attn-adapter-only+ft_ln-off"])
-def test_freeze_policy_flag_variants_vs_oracle(ds_attn, ds_ff, ft_ln):
+_WIDE = dict(hidden_size=512, num_attention_heads=8)  # the smallest width whose bottleneck H / 1 exceeds 256
+
+
+@pytest.mark.parametrize("ds_attn,ds_ff,ft_ln,width", [(0, 0, True, {}), (8, 8, False, {}), (0, 8, True, {}), (8, 0, False, {}),
+                                                       (1, 1, True, _WIDE), (1, 8, True, _WIDE)],
+                         ids=["no-adapters", "ft_ln-off", "ffn-adapter-only", "attn-adapter-only+ft_ln-off",
+                              "wide-bottlenecks", "wide-attn+narrow-ffn"])
+def test_freeze_policy_flag_variants_vs_oracle(ds_attn, ds_ff, ft_ln, width):
     """The constructor flags of the reference's ablations on the GPU: `ds_factor_attn / ds_factor_ff = 0` (no adapter at that
     site, model/deberta.py:252,326) and `ft_ln=False` (LayerNorms frozen, :1152-1158; args.py:333-337).  Trainable set = the
     reference's substring rule; logits / loss / every trainable gradient against the oracle (bf16-operand mode, the GPU's ReLU
-    gates), frozen parameters receive no gradient, train mode included (dropout masks replayed)."""
+    gates), frozen parameters receive no gradient, train mode included (dropout masks replayed).
+    The two wide cases (H = 512) are the only ones with a bottleneck above 256, where the adapter weight gradients are formed
+    one adapter at a time on the side stream instead of being parked for a grouped launch: A = 512 at both sites (merged GEMM,
+    fused tail, folded dx with an unpooled [dy | dz] operand), and A1 = 512 beside A2 = 64 (one backward mixes both routes)."""
     from tests.dropout_replay import ReplayedMasks
 
-    cfg = _tiny_cfg(ds_factor_attn=ds_attn, ds_factor_ff=ds_ff)
+    cfg = _tiny_cfg(ds_factor_attn=ds_attn, ds_factor_ff=ds_ff, **width)
     P = O.synth_params(cfg, seed=61, std=0.05, ln_jitter=0.1)
     B, Lt = 4, 50
     batch = synth_batch(cfg, B=B, L=Lt, seed=13)
@@ -696,6 +704,15 @@ def test_freeze_policy_flag_variants_vs_oracle(ds_attn, ds_ff, ft_ln):
         assert worst[0][0] < 2e-2, worst[:6]
         assert all(p.grad is None for n, p in m.named_parameters() if not p.requires_grad)
         del m, out, run
+
+
+@pytest.mark.parametrize("key", ["fuse_tail", "fold_dx", "dw_on_side", "merge", "side_stream"])
+def test_adapter_routes_are_not_engine_options(key):
+    """The adapter routes follow from the shapes alone: the keys that used to pick them by hand raise like any unknown key."""
+    cfg = _tiny_cfg()
+    m = build(cfg, O.synth_params(cfg, seed=61, std=0.05), engine_options={key: True})
+    with pytest.raises(ValueError, match="unknown engine_options.*" + key):
+        m.engine()
 
 
 @pytest.mark.slow
