@@ -10,7 +10,20 @@ allocations, one autograd node for the whole model.  The stages (reference lines
 
 Only linear_video and the LayerNorms under ``bert.`` train (freeze rule :547-553), so the backward forms dX through the
 transposed frozen weights (packed once) and accumulates dgamma / dbeta and the linear_video gradient into the flat buffer.
-No adapters, no launch graphs, no packed rows, no data parallelism on this path.
+
+Packed rows (opt-in ``model.packed_rows``, as on the DeBERTa engine): a call with labels or ``logit_rows`` outside a stream
+capture drops the trailing rows of every sample that nothing reads (``bert_packing``).  The embedding gather goes through
+the padded grid once; every GEMM and LayerNorm after it sees ``N = pk.n`` rows, the attention becomes fbl_mha_fwd_rows /
+fbl_mha_bwd_rows (``row0``; mask and lse stay on the grid), and the head maps its rows through ``pk.inv``.  Attention dropout
+draws the padded call's decisions; the row-wise sites are keyed by the packed element index (another, equally distributed
+mask stream).
+
+Data parallelism: the flat gradient buffer is preceded by ``parallel.SCALAR_SLOT`` floats and cut into one bucket per
+encoder layer plus one for the embeddings, in backward-completion order; ``backward`` tells an attached
+``parallel.GradReducer`` when a bucket is final (``ready``), where collectives may start (``window``: in front of each
+layer's attention backward) and when the step ends (``finish``).
+
+No adapters and no launch graphs on this path.
 """
 from __future__ import annotations
 
@@ -21,7 +34,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import lib as L
-from .engine import BF16, F32, Engine, NormRef, Run, Stream, _ru, _StepFn
+from .engine import BF16, F32, Engine, NormRef, Packing, Run, Stream, _ru, _StepFn
 
 
 @dataclass
@@ -44,6 +57,40 @@ def flat_order(nL: int, names: List[str]) -> List[str]:
         out += [n for n in names if n.startswith(f"bert.encoder.layer.{i}.")]
     out += [n for n in names if n not in set(out)]
     return out
+
+
+def bert_packing(mask, labels, logit_rows, B: int, S: int, T: int) -> Optional[Packing]:
+    """Packed-row layout of a BERT batch, or None when no row can be dropped.  mask: [B*S] (video mask | attention mask), labels:
+    int64 [B*S] on the grid (-100: none) or None, logit_rows: flat grid rows or None; any device (one host read of B integers).
+    plen[b] = max(last position with a valid token, a label or a requested logit row + 1, T, 1) -- and S for a sample whose
+    mask has no valid key: the additive mask makes such a sample attend to all S keys (Engine._make_packing may drop those
+    rows because XSoftmax zeroes them; BERT's mask does not)."""
+    dev = mask.device
+    valid = mask.reshape(B, S) != 0
+    keep = valid
+    if labels is not None:
+        keep = keep | (labels.reshape(B, S) != -100)
+    if logit_rows is not None:
+        want = torch.zeros(B * S, dtype=torch.bool, device=dev)
+        want[logit_rows.to(dev).long().reshape(-1)] = True
+        keep = keep | want.view(B, S)
+    pos1 = torch.arange(1, S + 1, device=dev, dtype=torch.int32)
+    last = (keep.to(torch.int32) * pos1).amax(1)
+    last = torch.where(valid.any(1), last, torch.full_like(last, S))
+    plen_h = [max(int(v), T, 1) for v in last.tolist()]
+    n = sum(plen_h)
+    if n >= B * S:
+        return None
+    offs = [0]
+    for v in plen_h:
+        offs.append(offs[-1] + v)
+    row0 = torch.tensor(offs, dtype=torch.int32, device=dev)
+    b_of = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(plen_h, device=dev), output_size=n)
+    pos = torch.arange(n, device=dev) - row0[:-1].long()[b_of]
+    sel = b_of * S + pos
+    inv = torch.full((B * S,), -1, dtype=torch.int64, device=dev)
+    inv[sel] = torch.arange(n, device=dev)
+    return Packing(row0=row0, sel=sel, inv=inv, pos=pos, n=n)
 
 
 class BertEngine:
@@ -91,7 +138,11 @@ class BertEngine:
             offs[n] = total
             total += _ru(named[n].numel(), 8)
         self.flat = torch.zeros(max(total, 8), dtype=F32, device=self.dev)
-        self.flat_grad = torch.zeros(max(total, 8), dtype=F32, device=self.dev)
+        # in front of the gradients: the floats that travel with the first data-parallel bucket (the step's logged loss)
+        from .parallel import SCALAR_SLOT
+
+        self.flat_grad_full = torch.zeros(SCALAR_SLOT + max(total, 8), dtype=F32, device=self.dev)
+        self.flat_grad = self.flat_grad_full[SCALAR_SLOT:]
         self.offsets, self.order, self.named = offs, order, named
         self.G: Dict[str, torch.Tensor] = {}
         for n in order:
@@ -102,6 +153,16 @@ class BertEngine:
             p.data = view
             self.G[n] = self.flat_grad[o:o + k].view(p.shape)
         self.P = {n: p.data for n, p in named.items()}
+        # one data-parallel bucket per backward stage: the encoder layers nL-1 .. 0, then the embeddings
+        self.bucket_ends: Dict[str, int] = {}
+        for n in order:
+            self.bucket_ends[self._bucket_key(n)] = offs[n] + _ru(named[n].numel(), 8)
+
+    @staticmethod
+    def _bucket_key(name: str) -> str:
+        if name.startswith("bert.encoder.layer."):
+            return "layer" + name.split(".")[3]
+        return "emb"
 
     def _pack_frozen(self):
         P, H = self.P, self.H
@@ -180,25 +241,40 @@ class BertEngine:
         else:
             mask = attention_mask
         mask = mask.to(torch.int32).contiguous()
+        full_labels = rows_labelled = None
+        if labels is not None:
+            fl = torch.cat([torch.full((B, T), -100, dtype=torch.long, device=self.dev), labels], 1) if use_video else labels
+            full_labels = fl.contiguous().view(-1)
+            rows_labelled = torch.nonzero(full_labels != -100).view(-1)
+        # packed rows (opt-in): only for calls whose outputs live on selected rows; the layout is a function of the input,
+        # read back before anything is queued (as Engine.run does it)
+        pk = None
+        if (getattr(m, "packed_rows", False) and (full_labels is not None or logit_rows is not None)
+                and not torch.cuda.is_current_stream_capturing()):
+            pk = bert_packing(mask.view(-1), full_labels, logit_rows, B, S, T)
         if train:
             m.step_seed += 1
         run = Run(B=B, S=S, T=T, Lt=Lt, train=train, save=need_grad, seed_base=m.dropout_seed_base() * 0x9E3779B1 & 0x7FFFFFFFFFFFFFFF
                   if train else 0, p_hid=self.cfg.hidden_dropout_prob if train else 0.0,
-                  p_att=self.cfg.attention_probs_dropout_prob if train else 0.0, p_ad=0.0)
+                  p_att=self.cfg.attention_probs_dropout_prob if train else 0.0, p_ad=0.0, pk=pk,
+                  N=pk.n if pk is not None else B * S)
         run.mask = mask.view(-1)
         pos1 = torch.arange(1, S + 1, device=self.dev, dtype=torch.int32)
         run.klen = (mask * pos1).amax(1).to(torch.int32).contiguous()
         run.border = torch.argsort(run.klen, descending=True, stable=True).to(torch.int32).contiguous()
-        run.labels = None
-        if labels is not None:
-            fl = torch.cat([torch.full((B, T), -100, dtype=torch.long, device=self.dev), labels], 1) if use_video else labels
-            run.labels = fl.contiguous().view(-1)
-            run.rows = torch.nonzero(run.labels != -100).view(-1)
+        run.labels = full_labels
+        if full_labels is not None:
+            run.rows = rows_labelled
+            if pk is not None:  # the head works on packed rows; the label values are looked up on the grid
+                run.label_rows = rows_labelled
+                run.rows = pk.inv[rows_labelled]
         use_ans = bool(m.n_ans) and not mlm
         if logit_rows is not None:
             if need_grad or labels is not None:
                 raise RuntimeError("logit_rows is an inference-time option (no labels, no gradient bookkeeping)")
             run.logit_rows = logit_rows.to(self.dev).to(torch.int32).contiguous().view(-1)
+            if pk is not None:
+                run.logit_rows = pk.inv[run.logit_rows.long()].to(torch.int32)
         with L.seed_word(None):
             logits, loss_t = self._forward(run, input_ids.contiguous(), video, use_ans, want_hidden)
         Vout = run.Vout
@@ -220,7 +296,7 @@ class BertEngine:
     def _forward(self, run, input_ids, video, use_ans, want_hidden):
         H, dev = self.H, self.dev
         B, S, T = run.B, run.S, run.T
-        N = B * S
+        pk, N = run.pk, run.N
         # ---- embeddings
         vproj = None
         if T:
@@ -229,9 +305,14 @@ class BertEngine:
             vproj = torch.empty(B * T, H, dtype=F32, device=dev)
             L.gemm(vb, self._video_weight(), bias=self.P["bert.embeddings.linear_video.bias"], out_f32=vproj)
             run.video_bf16 = vb
-        t0 = torch.empty(N, H, dtype=F32, device=dev)
+        t0 = torch.empty(B * S, H, dtype=F32, device=dev)
         L.embed_gather(input_ids, self.E32, vproj, T, t0)
-        emb, _ = self._ln(run, "bert.embeddings.LayerNorm", y=t0, resid=Stream(bf16=None, plain=self._pos_rows(B, S)), N=N,
+        if pk is None:
+            pos_rows = self._pos_rows(B, S)
+        else:  # packed rows: the gather went through the padded grid; the position of a row is pk.pos
+            t0 = t0.index_select(0, pk.sel)
+            pos_rows = self.pos_type.index_select(0, pk.pos)
+        emb, _ = self._ln(run, "bert.embeddings.LayerNorm", y=t0, resid=Stream(bf16=None, plain=pos_rows), N=N,
                           want_f32=run.p_hid > 0)
         run.emb_norm = emb.norm
         if run.p_hid > 0:  # post-LN dropout (:277): the layers see the materialised, dropped-out rows
@@ -244,7 +325,11 @@ class BertEngine:
             x = self._layer_fwd(run, i, x)
             hs.append(x)
         if want_hidden:
-            run.hidden_out = tuple(self._materialize(s).view(B, S, H) for s in hs)
+            if pk is None:
+                run.hidden_out = tuple(self._materialize(s).view(B, S, H) for s in hs)
+            else:  # (positions without a row read as zero)
+                run.hidden_out = tuple(torch.zeros(B * S, H, dtype=F32, device=dev).index_copy_(0, pk.sel, self._materialize(s))
+                                       .view(B, S, H) for s in hs)
         # ---- MLM / answer head
         if use_ans:
             Vout, table, bias = self.n_ans, self.Ansb, self.ans_bias
@@ -264,9 +349,9 @@ class BertEngine:
             return logits, None
         hp, hl = self._head_stage(run, x.bf16)
         run.head_pre, run.head_norm = hp, hl.norm
-        logits = torch.empty(N, ldv, dtype=F32, device=dev)
+        logits = torch.empty(B * S, ldv, dtype=F32, device=dev)  # (on the grid in both layouts)
         run.logits = logits
-        if run.labels is None:
+        if run.labels is None:  # (never packed: packing needs labels or logit_rows)
             L.gemm(hl.bf16, table, bias=bias, out_f32=logits, N=Vout)
             return logits, None
         # a loss is asked for: CE on the labelled rows from a small GEMM; the full logits are filled on first access
@@ -278,7 +363,7 @@ class BertEngine:
             L.gather_rows_bf16(hl.bf16, run.rows_i32, hrows)
             lc = torch.empty(R, ldv, dtype=F32, device=dev)
             L.gemm(hrows, table, bias=bias, out_f32=lc, N=Vout)
-            run.labels_c = run.labels[run.rows].contiguous()
+            run.labels_c = run.labels[run.rows if run.label_rows is None else run.label_rows].contiguous()
             run.row_lse = torch.empty(R, dtype=F32, device=dev)
             L.ce_fwd(lc, run.labels_c, Vout, run.row_lse, run.loss_acc)
             run.logits_c = lc
@@ -289,7 +374,17 @@ class BertEngine:
     def fill_logits(self, run):
         if run.logits_pending:
             run.logits_pending = False
-            L.gemm(run.head_ln_bf16, run.head_table, bias=run.head_bias, out_f32=run.logits, N=run.Vout)
+            pk = run.pk
+            if pk is None:
+                L.gemm(run.head_ln_bf16, run.head_table, bias=run.head_bias, out_f32=run.logits, N=run.Vout)
+                return
+            # packed rows: grid positions without a row read as zero; the others arrive in slabs of 1024 rows
+            run.logits.zero_()
+            for r0 in range(0, pk.n, 1024):
+                r1 = min(pk.n, r0 + 1024)
+                slab = torch.empty(r1 - r0, run.logits.shape[1], dtype=F32, device=self.dev)
+                L.gemm(run.head_ln_bf16[r0:r1], run.head_table, bias=run.head_bias, out_f32=slab, N=run.Vout)
+                run.logits.index_copy_(0, pk.sel[r0:r1], slab)
 
     def _head_stage(self, run, hin):
         """BertPredictionHeadTransform (:67-71): LayerNorm(gelu(dense(x)))"""
@@ -304,15 +399,19 @@ class BertEngine:
     def _layer_fwd(self, run, li: int, x: Stream) -> Stream:
         w, H, I, dev = self.Lw[li], self.H, self.I, self.dev
         B, S, nh = run.B, run.S, self.nh
-        N = B * S
+        N = run.N
         p = f"bert.encoder.layer.{li}."
         qkv = torch.empty(N, 3 * H, dtype=BF16, device=dev)
         L.gemm(x.bf16, w["Wqkv"], bias=w["bqkv"], out_bf16=qkv)
         ctx = torch.empty(N, H, dtype=BF16, device=dev)
         lse = torch.empty(B, nh, S, dtype=F32, device=dev)
         seed_att = run.next_seed() if run.p_att > 0 else 0
-        L.mha_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], run.mask, self.scale, ctx, lse, B, S, nh, p_drop=run.p_att,
-                  seed=seed_att, klen=run.klen, border=run.border)
+        if run.pk is None:
+            L.mha_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], run.mask, self.scale, ctx, lse, B, S, nh, p_drop=run.p_att,
+                      seed=seed_att, klen=run.klen, border=run.border)
+        else:
+            L.mha_fwd_rows(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], run.mask, run.klen, run.pk.row0, self.scale, ctx, lse, B, S,
+                           nh, p_drop=run.p_att, seed=seed_att, border=run.border)
         y1 = torch.empty(N, H, dtype=F32, device=dev)
         L.gemm(ctx, w["Wo"], bias=w["bo"], out_f32=y1)
         a, seed1 = self._ln(run, p + "attention.output.LayerNorm", y=y1, resid=x, N=N, p_drop=run.p_hid)
@@ -332,9 +431,10 @@ class BertEngine:
             raise RuntimeError("forward was run without gradient bookkeeping")
         H, dev = self.H, self.dev
         B, S, T = run.B, run.S, run.T
-        N = B * S
+        pk, N = run.pk, run.N
         if attach:
             self.attach_grads()
+        red = self.reducer  # data parallel: told when a stage's bucket is final, where collectives may start, when the step ends
         dx = L.zeros(N, H, dtype=F32, device=dev)
         Vout = run.Vout
         Vp = _ru(Vout, 64)
@@ -346,23 +446,32 @@ class BertEngine:
             L.ce_bwd_rows(run.logits_c, run.labels_c, ar, Vout, Vp, run.row_lse, run.loss_acc, gs, dlog)
             dx = self._head_bwd(run, run.rows_i32, dlog, dx)
         if glogits is not None:
+            gl = glogits.reshape(B * S, Vout)
+            if pk is not None:  # (gradients handed in at positions without a row have nothing to flow into)
+                gl = gl.index_select(0, pk.sel)
             dlog = torch.zeros(N, Vp, dtype=BF16, device=dev)
-            dlog[:, :Vout].copy_(glogits.reshape(N, Vout))
+            dlog[:, :Vout].copy_(gl)
             dx = self._head_bwd(run, None, dlog, dx)
         for li in reversed(range(self.nL)):
             dx = self._layer_bwd(run, li, run.layers[li], dx)
+            if red is not None:
+                red.ready(f"layer{li}")
         run.layers.clear()
         # ---- embeddings: post-LN dropout, LayerNorm (dgamma / dbeta), linear_video on the video rows
         if run.p_hid > 0:
             L.dropout_f32(dx, run.p_hid, run.seed_emb, out_f32=dx)
         dt, dyb = self._ln_bwd("bert.embeddings.LayerNorm", dx, run.emb_norm, 0.0, 0, want_dy_bf16=bool(T))
         if T and "bert.embeddings.linear_video.weight" in self.G:
-            vrows = (torch.arange(B, device=dev, dtype=torch.int32)[:, None] * S
-                     + torch.arange(T, device=dev, dtype=torch.int32)[None, :]).view(-1).contiguous()
+            # the video slots are the first T rows of every sample (packed rows: plen >= T)
+            first = torch.arange(B, device=dev, dtype=torch.int32) * S if pk is None else pk.row0[:-1]
+            vrows = (first[:, None] + torch.arange(T, device=dev, dtype=torch.int32)[None, :]).view(-1).contiguous()
             dv = torch.empty(B * T, H, dtype=BF16, device=dev)
             L.gather_rows_bf16(dyb, vrows, dv)
             L.gemm_tn_acc(dv, run.video_bf16, self.G["bert.embeddings.linear_video.weight"], self.sk_ws, M=H, N=self.F)
             L.colsum(dv, self.G["bert.embeddings.linear_video.bias"], self._cs_ws)
+        if red is not None:
+            red.ready("emb")
+            red.finish()
 
     def _head_bwd(self, run, rows, dlog, dx):
         """dx[rows] += d/d(head input) for the bf16 logit gradients dlog [R, Vp] of those rows (rows None: every row); returns dx"""
@@ -397,7 +506,7 @@ class BertEngine:
         """dout: gradient of the layer's output (fp32 [N, H]); returns the gradient of its input"""
         w, H, I, dev = self.Lw[li], self.H, self.I, self.dev
         B, S, nh = run.B, run.S, self.nh
-        N = B * S
+        N = run.N
         p = f"bert.encoder.layer.{li}."
         dt2, dy2 = self._ln_bwd(p + "output.LayerNorm", dout, sv.ln2, run.p_hid, sv.seed_ln2)
         dh = torch.empty(N, I, dtype=BF16, device=dev)
@@ -408,11 +517,18 @@ class BertEngine:
         dctx = torch.empty(N, H, dtype=BF16, device=dev)
         L.gemm(dy1, w["WoT"], out_bf16=dctx)
         Dv = torch.empty(B, nh, S, dtype=F32, device=dev)
-        L.attn_rowdot(dctx, sv.ctx, Dv, B, S, nh)
         dqkv = torch.empty(N, 3 * H, dtype=BF16, device=dev)
         q = sv.qkv
-        L.mha_bwd(q[:, :H], q[:, H:2 * H], q[:, 2 * H:], dctx, run.mask, sv.lse, Dv, self.scale, dqkv[:, :H], dqkv[:, H:2 * H],
-                  dqkv[:, 2 * H:], B, S, nh, p_drop=run.p_att, seed=sv.seed_att, klen=run.klen, border=run.border)
+        if self.reducer is not None:  # a stretch without one-workgroup-per-CU GEMM tiles: where gradient collectives may start
+            self.reducer.window()
+        if run.pk is None:
+            L.attn_rowdot(dctx, sv.ctx, Dv, B, S, nh)
+            L.mha_bwd(q[:, :H], q[:, H:2 * H], q[:, 2 * H:], dctx, run.mask, sv.lse, Dv, self.scale, dqkv[:, :H], dqkv[:, H:2 * H],
+                      dqkv[:, 2 * H:], B, S, nh, p_drop=run.p_att, seed=sv.seed_att, klen=run.klen, border=run.border)
+        else:
+            L.mha_bwd_rows(q[:, :H], q[:, H:2 * H], q[:, 2 * H:], dctx, sv.ctx, run.mask, run.klen, run.pk.row0, sv.lse, Dv,
+                           self.scale, dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:], B, S, nh, p_drop=run.p_att,
+                           seed=sv.seed_att, border=run.border)
         dx = torch.empty(N, H, dtype=F32, device=dev)
         L.gemm(dqkv, w["WqkvT"], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dx)
         return dx

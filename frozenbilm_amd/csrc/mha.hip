@@ -28,6 +28,7 @@ struct MhaArgs {
   const int32_t* mask;
   const int32_t* klen;
   const int32_t* border;
+  const int32_t* row0;  // packed rows (fbl_mha_*_rows): sample b owns the activation rows [row0[b], row0[b+1]); nullptr: b*S
   const float* lse;
   const float* Dv;
   float scale, p_drop;
@@ -54,18 +55,34 @@ __device__ __forceinline__ int key_limit(const int32_t* klen, int b, int S) {
   return kl > 0 ? kl : S;
 }
 
-__device__ __forceinline__ float key_bias(int j, int S, int m) {
-  return j < S ? (m != 0 ? 0.f : MASK_BIAS) : -INFINITY;
+__device__ __forceinline__ float key_bias(int j, int pl, int m) {
+  return j < pl ? (m != 0 ? 0.f : MASK_BIAS) : -INFINITY;
+}
+
+// The activation rows of sample b (q / k / v / ctx / dO / dQ / dK / dV): first row and how many of its S positions have one.
+// The mask, lse and D keep the padded [B, S] indexing in both layouts.
+struct Rows { long rb; int pl; };
+__device__ __forceinline__ Rows sample_rows(const int32_t* row0, int b, int S) {
+  Rows r;
+  if (row0) {
+    const int r0 = row0[b];
+    r.rb = r0;
+    r.pl = min(row0[b + 1] - r0, S);  // (<= 0: the sample has no row, its workgroups do nothing)
+  } else {
+    r.rb = (long)b * S;
+    r.pl = S;
+  }
+  return r;
 }
 
 struct Pair { bf16x8 x[2], y[2]; int km; };
 
 // the 64 x 64 bf16 tiles of two tensors (rows r0 .. r0+63 of this sample, clamped to the last row) into registers
-__device__ __forceinline__ void load_pair(Pair& R, const bf16* x, long ldx, const bf16* y, long ldy, long rb, int r0, int S,
+__device__ __forceinline__ void load_pair(Pair& R, const bf16* x, long ldx, const bf16* y, long ldy, long rb, int r0, int pl,
                                           int col, int srow, int sch) {
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    const long r = rb + min(r0 + srow + t * 32, S - 1);
+    const long r = rb + min(r0 + srow + t * 32, pl - 1);
     R.x[t] = *(const bf16x8*)(x + r * ldx + col + sch * 8);
     R.y[t] = *(const bf16x8*)(y + r * ldy + col + sch * 8);
   }
@@ -135,8 +152,11 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_kernel(MhaArgs a) {
   const WgCoord wc = wg_coord(Sp / 64, a.nh, a.B, a.border);
   const int i0 = wc.x * 64, h = wc.h, b = wc.b;
   const int i = i0 + w * 16 + c;  // this lane's query row
-  const long rb = (long)b * S;
-  const int nkt = (key_limit(a.klen, b, S) + 63) / 64;
+  const Rows rw = sample_rows(a.row0, b, S);
+  const long rb = rw.rb, mb = (long)b * S;
+  const int pl = rw.pl;
+  if (i0 >= pl) return;  // (packed rows: a query tile the sample has no row of)
+  const int nkt = (min(key_limit(a.klen, b, S), pl) + 63) / 64;
   float* kb = (float*)(smem + SM_F0);
 
   const DropKey dk = attn_drop_key(a.p_drop > 0.f ? fbl_seed(a.seed, a.seed_dev) : 0, b * a.nh + h, a.p_drop);
@@ -146,11 +166,11 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_kernel(MhaArgs a) {
   const int sb = srow * 128 + ((sch ^ (srow & 7)) << 4);
 
   Pair R;
-  load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, 0, S, h * 64, srow, sch);
-  R.km = a.mask[rb + min(lane, S - 1)];
+  load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, 0, pl, h * 64, srow, sch);
+  R.km = a.mask[mb + min(lane, S - 1)];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
-    *(bf16x8*)(smem + SM_QS + sb + t * 4096) = *(const bf16x8*)(a.q + (rb + min(i0 + srow + t * 32, S - 1)) * a.ldq + h * 64 + sch * 8);
+    *(bf16x8*)(smem + SM_QS + sb + t * 4096) = *(const bf16x8*)(a.q + (rb + min(i0 + srow + t * 32, pl - 1)) * a.ldq + h * 64 + sch * 8);
 
   float m_run = -INFINITY, l_run = 0.f;
   f32x4 o[4];
@@ -160,12 +180,12 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_kernel(MhaArgs a) {
   for (int jt = 0; jt < nkt; ++jt) {
     const int j0 = jt * 64;
     store_pair(smem, R, sb);
-    if (tid < 64) kb[tid] = key_bias(j0 + tid, S, R.km);
+    if (tid < 64) kb[tid] = key_bias(j0 + tid, pl, R.km);
     __syncthreads();  // K / V tile, key bias (and, first time round, the Q tile) visible
     {  // next tile in flight during this one (unconditional: behind a branch later waits could not count the requests)
       const int jn = min(jt + 1, nkt - 1) * 64;
-      load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, jn, S, h * 64, srow, sch);
-      R.km = a.mask[rb + min(jn + lane, S - 1)];
+      load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, jn, pl, h * 64, srow, sch);
+      R.km = a.mask[mb + min(jn + lane, S - 1)];
     }
     // ---- scores, transposed: sacc[nt][r] = Q_i . K_j,  j = j0 + nt*16 + g*4 + r
     f32x4 sacc[4];
@@ -191,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_kernel(MhaArgs a) {
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);  // finite: key j0 < S of every visited tile has a finite score
+    const float m_new = fmaxf(m_run, mx);  // finite: key j0 < pl of every visited tile has a finite score
     const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
     float psum = 0.f;
 #pragma unroll
@@ -220,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_kernel(MhaArgs a) {
     __syncthreads();  // the tiles are overwritten by the next key tile
   }
 
-  if (i < S) {
+  if (i < pl) {
     const float inv_l = 1.f / l_run;
     bf16* op = a.out0 + (rb + i) * a.ld0 + h * 64 + g * 4;
 #pragma unroll
@@ -244,9 +264,12 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkdv_kernel(MhaArgs a) {
   const WgCoord wc = wg_coord(Sp / 64, a.nh, a.B, a.border);
   const int j0 = wc.x * 64, h = wc.h, b = wc.b;
   const int j = j0 + w * 16 + c;  // this lane's key
-  const long rb = (long)b * S;
-  const int kl = key_limit(a.klen, b, S);
-  const int nqt = Sp / 64;
+  const Rows rw = sample_rows(a.row0, b, S);
+  const long rb = rw.rb, mb = (long)b * S;
+  const int pl = rw.pl;
+  if (j0 >= pl) return;  // (packed rows: a key tile the sample has no row of)
+  const int kl = min(key_limit(a.klen, b, S), pl);
+  const int nqt = (pl + 63) / 64;  // (query rows the sample does not have carry dO = 0: they add exact zeros)
   float* lse2 = (float*)(smem + SM_F0);
   float* Ds = (float*)(smem + SM_F1);
 
@@ -255,12 +278,12 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkdv_kernel(MhaArgs a) {
   for (int dt = 0; dt < 4; ++dt) dv[dt] = dkk[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   if (j0 < (kl + 63) / 64 * 64) {  // (key tiles the forward skipped have P = 0: dK = dV = 0)
-    const int jc = min(j, S - 1);
+    const int jc = min(j, pl - 1);
     const bf16* kr = a.k + (rb + jc) * a.ldk + h * 64 + g * 8;
     const bf16* vr = a.v + (rb + jc) * a.ldv + h * 64 + g * 8;
     const bf16x8 kf0 = *(const bf16x8*)kr, kf1 = *(const bf16x8*)(kr + 32);
     const bf16x8 vf0 = *(const bf16x8*)vr, vf1 = *(const bf16x8*)(vr + 32);
-    const float kbias = key_bias(j, S, a.mask[rb + jc]);
+    const float kbias = key_bias(j, pl, a.mask[mb + min(j, S - 1)]);
     const DropKey dk = attn_drop_key(a.p_drop > 0.f ? fbl_seed(a.seed, a.seed_dev) : 0, b * a.nh + h, a.p_drop);
     const float k2 = a.scale * LOG2E;
     const int srow = tid >> 3, sch = tid & 7;
@@ -270,22 +293,22 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkdv_kernel(MhaArgs a) {
     const float* D_bh = a.Dv + ((long)b * a.nh + h) * S;
 
     Pair R;
-    load_pair(R, a.q, a.ldq, a.dO, a.lddo, rb, 0, S, h * 64, srow, sch);
+    load_pair(R, a.q, a.ldq, a.dO, a.lddo, rb, 0, pl, h * 64, srow, sch);
     float lq = 0.f, dq = 0.f;
-    if (tid < 64) { lq = lse_bh[min(tid, S - 1)]; dq = D_bh[min(tid, S - 1)]; }
+    if (tid < 64) { lq = lse_bh[min(tid, pl - 1)]; dq = D_bh[min(tid, pl - 1)]; }
     for (int it = 0; it < nqt; ++it) {
       const int i0 = it * 64;
       store_pair(smem, R, sb);
       if (tid < 64) {
-        const bool live = i0 + tid < S;
+        const bool live = i0 + tid < pl;
         lse2[tid] = live ? lq * LOG2E : INFINITY;  // padding query rows: P = 0
         Ds[tid] = live ? dq : 0.f;
       }
       __syncthreads();
       {
         const int in = min(it + 1, nqt - 1) * 64;
-        load_pair(R, a.q, a.ldq, a.dO, a.lddo, rb, in, S, h * 64, srow, sch);
-        if (tid < 64) { lq = lse_bh[min(in + tid, S - 1)]; dq = D_bh[min(in + tid, S - 1)]; }
+        load_pair(R, a.q, a.ldq, a.dO, a.lddo, rb, in, pl, h * 64, srow, sch);
+        if (tid < 64) { lq = lse_bh[min(in + tid, pl - 1)]; dq = D_bh[min(in + tid, pl - 1)]; }
       }
       float p[16], ds[16];
 #pragma unroll
@@ -327,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dkdv_kernel(MhaArgs a) {
       __syncthreads();
     }
   }
-  if (j < S) {
+  if (j < pl) {
     bf16* kp = a.out0 + (rb + j) * a.ld0 + h * 64 + g * 4;
     bf16* vp = a.out1 + (rb + j) * a.ld1 + h * 64 + g * 4;
 #pragma unroll
@@ -349,17 +372,20 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_kernel(MhaArgs a) {
   const WgCoord wc = wg_coord(Sp / 64, a.nh, a.B, a.border);
   const int i0 = wc.x * 64, h = wc.h, b = wc.b;
   const int i = i0 + w * 16 + c;  // this lane's query
-  const long rb = (long)b * S;
-  const int nkt = (key_limit(a.klen, b, S) + 63) / 64;
+  const Rows rw = sample_rows(a.row0, b, S);
+  const long rb = rw.rb, mb = (long)b * S;
+  const int pl = rw.pl;
+  if (i0 >= pl) return;
+  const int nkt = (min(key_limit(a.klen, b, S), pl) + 63) / 64;
   float* kb = (float*)(smem + SM_F0);
 
-  const int ic = min(i, S - 1);
+  const int ic = min(i, pl - 1);
   const bf16* qr = a.q + (rb + ic) * a.ldq + h * 64 + g * 8;
   const bf16* orow = a.dO + (rb + ic) * a.lddo + h * 64 + g * 8;
   const bf16x8 qf0 = *(const bf16x8*)qr, qf1 = *(const bf16x8*)(qr + 32);
   const bf16x8 of0 = *(const bf16x8*)orow, of1 = *(const bf16x8*)(orow + 32);
-  const float lse2 = i < S ? a.lse[((long)b * a.nh + h) * S + i] * LOG2E : INFINITY;
-  const float Di = i < S ? a.Dv[((long)b * a.nh + h) * S + i] : 0.f;
+  const float lse2 = i < pl ? a.lse[((long)b * a.nh + h) * S + i] * LOG2E : INFINITY;
+  const float Di = i < pl ? a.Dv[((long)b * a.nh + h) * S + i] : 0.f;
   const DropKey dk = attn_drop_key(a.p_drop > 0.f ? fbl_seed(a.seed, a.seed_dev) : 0, b * a.nh + h, a.p_drop);
   const float k2 = a.scale * LOG2E;
   const int srow = tid >> 3, sch = tid & 7;
@@ -370,17 +396,17 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_kernel(MhaArgs a) {
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dqa[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   Pair R;
-  load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, 0, S, h * 64, srow, sch);
-  R.km = a.mask[rb + min(lane, S - 1)];
+  load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, 0, pl, h * 64, srow, sch);
+  R.km = a.mask[mb + min(lane, S - 1)];
   for (int jt = 0; jt < nkt; ++jt) {
     const int j0 = jt * 64;
     store_pair(smem, R, sb);
-    if (tid < 64) kb[tid] = key_bias(j0 + tid, S, R.km);
+    if (tid < 64) kb[tid] = key_bias(j0 + tid, pl, R.km);
     __syncthreads();
     {
       const int jn = min(jt + 1, nkt - 1) * 64;
-      load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, jn, S, h * 64, srow, sch);
-      R.km = a.mask[rb + min(jn + lane, S - 1)];
+      load_pair(R, a.k, a.ldk, a.v, a.ldv, rb, jn, pl, h * 64, srow, sch);
+      R.km = a.mask[mb + min(jn + lane, S - 1)];
     }
     float p[16], ds[16];
 #pragma unroll
@@ -411,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_kernel(MhaArgs a) {
     }
     __syncthreads();
   }
-  if (i < S) {
+  if (i < pl) {
     bf16* qp = a.out0 + (rb + i) * a.ld0 + h * 64 + g * 4;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
@@ -419,12 +445,36 @@ __global__ __launch_bounds__(256, 2) void mha_bwd_dq_kernel(MhaArgs a) {
   }
 }
 
-}  // namespace
+// D[b,h,s] = dO_row . O_row for the rows that exist (packed layout): the lane arrangement and the summation order of
+// fbl_attn_rowdot (8 lanes per (row, head), 3-step shuffle reduction), so the values are its values bit for bit.
+__global__ void mha_rowdot_rows_kernel(const bf16* dO, long lddo, const bf16* O, long ldo, const int32_t* row0, float* out,
+                                       int B, int S, int nh) {
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long idx = gid >> 3;  // (padded row, head)
+  const int c = (int)(gid & 7);
+  const long total = (long)B * S * nh;
+  const long prow = idx < total ? idx / nh : 0;
+  const int h = idx < total ? (int)(idx % nh) : 0;
+  const int bb = (int)(prow / S), ss = (int)(prow % S);
+  const int r0 = row0[bb];
+  const bool live = idx < total && ss < row0[bb + 1] - r0;
+  float s = 0.f;
+  if (live) {
+    const long row = (long)r0 + ss;
+    const bf16x8 x = *(const bf16x8*)(dO + row * lddo + h * 64 + c * 8);
+    const bf16x8 y = *(const bf16x8*)(O + row * ldo + h * 64 + c * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += bf2f(x[e]) * bf2f(y[e]);
+  }
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 4, 64);
+  if (live && c == 0) out[((long)bb * nh + h) * S + ss] = s;
+}
 
-extern "C" int fbl_mha_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                           const int32_t* mask, const int32_t* klen, const int32_t* border, float scale, float p_drop,
-                           uint64_t seed, const uint64_t* seed_dev, void* ctx, int64_t ldo, float* lse, int B, int S, int nh,
-                           void* stream) {
+int mha_fwd_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const int32_t* mask,
+                   const int32_t* klen, const int32_t* border, const int32_t* row0, float scale, float p_drop, uint64_t seed,
+                   const uint64_t* seed_dev, void* ctx, int64_t ldo, float* lse, int B, int S, int nh, void* stream) {
   if (S < 1 || S > 512) return FBL_ERR_SHAPE;
   if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 4)) return FBL_ERR_ALIGN;
   if (!q || !k || !v || !mask || !ctx || !lse || p_drop < 0.f || p_drop >= 1.f) return FBL_ERR_ARG;
@@ -432,7 +482,7 @@ extern "C" int fbl_mha_fwd(const void* q, int64_t ldq, const void* k, int64_t ld
   MhaArgs a{};
   a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
-  a.mask = mask; a.klen = klen; a.border = border;
+  a.mask = mask; a.klen = klen; a.border = border; a.row0 = row0;
   a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
   a.out0 = (bf16*)ctx; a.ld0 = ldo; a.lse_out = lse;
   a.B = B; a.S = S; a.nh = nh;
@@ -441,19 +491,28 @@ extern "C" int fbl_mha_fwd(const void* q, int64_t ldq, const void* k, int64_t ld
   return 0;
 }
 
-extern "C" int fbl_mha_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                           const void* dO, int64_t lddo, const int32_t* mask, const int32_t* klen, const int32_t* border,
-                           const float* lse, const float* Dv, float scale, float p_drop, uint64_t seed,
-                           const uint64_t* seed_dev, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv,
-                           int B, int S, int nh, void* stream) {
+// (Dv: read by the two passes; with row0 it is also formed here first, from dO and O)
+int mha_bwd_launch(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* dO,
+                   int64_t lddo, const void* O, int64_t ldo, const int32_t* mask, const int32_t* klen, const int32_t* border,
+                   const int32_t* row0, const float* lse, float* Dv, float scale, float p_drop, uint64_t seed,
+                   const uint64_t* seed_dev, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, int B, int S,
+                   int nh, void* stream) {
   if (S < 1 || S > 512) return FBL_ERR_SHAPE;
   if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (lddo % 8) || (lddq % 4) || (lddk % 4) || (lddv % 4)) return FBL_ERR_ALIGN;
+  if (row0 && (ldo % 8)) return FBL_ERR_ALIGN;
   if (!q || !k || !v || !dO || !mask || !lse || !Dv || !dQ || !dK || !dV || p_drop < 0.f || p_drop >= 1.f) return FBL_ERR_ARG;
+  if (row0 && !O) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
+  if (row0) {
+    const long total = (long)B * S * nh;
+    hipLaunchKernelGGL(mha_rowdot_rows_kernel, dim3((unsigned)((total * 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16*)dO, (long)lddo, (const bf16*)O, (long)ldo, row0, Dv, B, S, nh);
+    FBL_CHECK_LAUNCH();
+  }
   MhaArgs a{};
   a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.dO = (const bf16*)dO;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.lddo = lddo;
-  a.mask = mask; a.klen = klen; a.border = border; a.lse = lse; a.Dv = Dv;
+  a.mask = mask; a.klen = klen; a.border = border; a.row0 = row0; a.lse = lse; a.Dv = Dv;
   a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
   a.B = B; a.S = S; a.nh = nh;
   const dim3 grid((unsigned)((S + 63) / 64 * nh * B));
@@ -464,4 +523,44 @@ extern "C" int fbl_mha_bwd(const void* q, int64_t ldq, const void* k, int64_t ld
   hipLaunchKernelGGL(mha_bwd_dq_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   FBL_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int fbl_mha_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                           const int32_t* mask, const int32_t* klen, const int32_t* border, float scale, float p_drop,
+                           uint64_t seed, const uint64_t* seed_dev, void* ctx, int64_t ldo, float* lse, int B, int S, int nh,
+                           void* stream) {
+  return mha_fwd_launch(q, ldq, k, ldk, v, ldv, mask, klen, border, nullptr, scale, p_drop, seed, seed_dev, ctx, ldo, lse, B, S,
+                        nh, stream);
+}
+
+extern "C" int fbl_mha_fwd_rows(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                const int32_t* mask, const int32_t* klen, const int32_t* border, const int32_t* row0, float scale,
+                                float p_drop, uint64_t seed, const uint64_t* seed_dev, void* ctx, int64_t ldo, float* lse, int B,
+                                int S, int nh, void* stream) {
+  if (S < 1 || S > 512) return FBL_ERR_SHAPE;
+  if (!row0 || !klen) return FBL_ERR_ARG;
+  return mha_fwd_launch(q, ldq, k, ldk, v, ldv, mask, klen, border, row0, scale, p_drop, seed, seed_dev, ctx, ldo, lse, B, S, nh,
+                        stream);
+}
+
+extern "C" int fbl_mha_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                           const void* dO, int64_t lddo, const int32_t* mask, const int32_t* klen, const int32_t* border,
+                           const float* lse, const float* Dv, float scale, float p_drop, uint64_t seed,
+                           const uint64_t* seed_dev, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv,
+                           int B, int S, int nh, void* stream) {
+  return mha_bwd_launch(q, ldq, k, ldk, v, ldv, dO, lddo, nullptr, 0, mask, klen, border, nullptr, lse, (float*)Dv, scale, p_drop,
+                        seed, seed_dev, dQ, lddq, dK, lddk, dV, lddv, B, S, nh, stream);
+}
+
+extern "C" int fbl_mha_bwd_rows(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                const void* dO, int64_t lddo, const void* O, int64_t ldo, const int32_t* mask,
+                                const int32_t* klen, const int32_t* border, const int32_t* row0, const float* lse, float* Dv,
+                                float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* dQ, int64_t lddq,
+                                void* dK, int64_t lddk, void* dV, int64_t lddv, int B, int S, int nh, void* stream) {
+  if (S < 1 || S > 512) return FBL_ERR_SHAPE;
+  if (!row0 || !klen || !O) return FBL_ERR_ARG;
+  return mha_bwd_launch(q, ldq, k, ldk, v, ldv, dO, lddo, O, ldo, mask, klen, border, row0, lse, Dv, scale, p_drop, seed,
+                        seed_dev, dQ, lddq, dK, lddk, dV, lddv, B, S, nh, stream);
 }

@@ -84,6 +84,9 @@ MHA_SIGNATURES = {
     "fbl_mha_fwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _i, _i, _i, _vp]),
     "fbl_mha_bwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l, _vp, _l,
                          _i, _i, _i, _vp]),
+    "fbl_mha_fwd_rows": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _i, _i, _i, _vp]),
+    "fbl_mha_bwd_rows": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l,
+                              _vp, _l, _vp, _l, _i, _i, _i, _vp]),
 }
 
 _LIB = None
@@ -781,3 +784,40 @@ def mha_bwd(q, k, v, dO, mask, lse, Dv, scale, dQ, dK, dV, B, S, nh, p_drop=0.0,
                             _p(mask), _p(klen), _p(border), _p(lse), _p(Dv), float(scale), float(p_drop), int(seed), _seed_dev(),
                             _p(dQ), _rows2d(dQ, "dQ"), _p(dK), _rows2d(dK, "dK"), _p(dV), _rows2d(dV, "dV"), B, S, nh, _stream()),
          "fbl_mha_bwd")
+
+
+def _mha_rows_args(row0, klen, border, B):
+    for t, n, k in ((row0, "row0", B + 1), (klen, "klen", B), (border, "border", B)):
+        if t is None:
+            if n == "border":
+                continue
+            raise ValueError(f"the packed-row attention needs {n}")
+        _req(t, torch.int32, n)
+        assert t.is_contiguous() and t.numel() == k
+
+
+def mha_fwd_rows(q, k, v, mask, klen, row0, scale, ctx, lse, B, S, nh, p_drop=0.0, seed=0, border=None):
+    """mha_fwd on packed rows: sample b owns the rows [row0[b], row0[b+1]) of q / k / v / ctx; mask [B*S] and lse [B,nh,S] stay
+    on the padded grid (include/fbl_mha.h)"""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx")):
+        _req(t, torch.bfloat16, n)
+    _req(mask, torch.int32, "mask"); _req(lse, torch.float32, "lse")
+    assert mask.is_contiguous() and mask.numel() == B * S and lse.is_contiguous() and lse.numel() == B * nh * S
+    _mha_rows_args(row0, klen, border, B)
+    _chk(load().fbl_mha_fwd_rows(_p(q), _rows2d(q, "q"), _p(k), _rows2d(k, "k"), _p(v), _rows2d(v, "v"), _p(mask), _p(klen),
+                                 _p(border), _p(row0), float(scale), float(p_drop), int(seed), _seed_dev(), _p(ctx),
+                                 _rows2d(ctx, "ctx"), _p(lse), B, S, nh, _stream()), "fbl_mha_fwd_rows")
+
+
+def mha_bwd_rows(q, k, v, dO, O, mask, klen, row0, lse, Dv, scale, dQ, dK, dV, B, S, nh, p_drop=0.0, seed=0, border=None):
+    """mha_bwd on packed rows; Dv fp32 [B,nh,S] is scratch, written here from dO and the forward's output O"""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (dO, "dO"), (O, "O"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")):
+        _req(t, torch.bfloat16, n)
+    _req(mask, torch.int32, "mask"); _req(lse, torch.float32, "lse"); _req(Dv, torch.float32, "Dv")
+    assert mask.is_contiguous() and lse.is_contiguous() and Dv.is_contiguous()
+    assert mask.numel() == B * S and lse.numel() == B * nh * S and Dv.numel() == B * nh * S
+    _mha_rows_args(row0, klen, border, B)
+    _chk(load().fbl_mha_bwd_rows(_p(q), _rows2d(q, "q"), _p(k), _rows2d(k, "k"), _p(v), _rows2d(v, "v"), _p(dO), _rows2d(dO, "dO"),
+                                 _p(O), _rows2d(O, "O"), _p(mask), _p(klen), _p(border), _p(row0), _p(lse), _p(Dv), float(scale),
+                                 float(p_drop), int(seed), _seed_dev(), _p(dQ), _rows2d(dQ, "dQ"), _p(dK), _rows2d(dK, "dK"),
+                                 _p(dV), _rows2d(dV, "dV"), B, S, nh, _stream()), "fbl_mha_bwd_rows")

@@ -121,7 +121,8 @@ class BertForMaskedLM(nn.Module):
         self._module("bert.embeddings").register_buffer("position_ids",
                                                         torch.arange(cfg.max_position_embeddings).expand((1, -1)))
         self._engine = None
-        # opt-in attributes the loops set on the DeBERTa model: accepted, this path runs them eagerly
+        # opt-in attributes the loops set on the DeBERTa model: the launch graphs are accepted and this path runs eagerly;
+        # packed_rows is honoured (bert_engine.bert_packing)
         self.inference_graphs = False
         self.training_graphs = False
         self.packed_rows = False
@@ -165,6 +166,8 @@ class BertForMaskedLM(nn.Module):
             from ..bert_engine import BertEngine
 
             self._engine = BertEngine(self)
+            if self._reducer is not None:
+                self._reducer.rebind(self._engine)
         return self._engine
 
     def set_answer_embeddings(self, a2tok, freeze_last=True):

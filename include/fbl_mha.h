@@ -38,6 +38,32 @@ int fbl_mha_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const vo
                 const float* Dv, float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* dQ, int64_t lddq,
                 void* dK, int64_t lddk, void* dV, int64_t lddv, int B, int S, int nh, void* stream);
 
+/* fbl_mha_fwd / fbl_mha_bwd on PACKED ROWS: the activation rows of a ragged batch without its trailing padding.
+ *   row0 int32 [B+1] (required): sample b owns the rows [row0[b], row0[b+1]) of q / k / v / ctx / dO / O / dQ / dK / dV -- its
+ *   positions 0 .. plen[b]-1, plen[b] = row0[b+1] - row0[b] <= S.  klen is required, and plen[b] >= klen[b].  mask, lse and
+ *   Dv keep their padded [B,S] / [B,nh,S] indexing.  Rows a sample does not have are neither read nor written: loads clamp
+ *   to the sample's last row, keys j >= plen[b] get a -inf bias, query and key tiles wholly beyond plen[b] do nothing, and
+ *   lse / Dv are written at positions < plen[b] only.
+ *   A sample with klen[b] == 0 has no valid key and softmaxes over all S keys (as the reference does): the caller must give
+ *   such a sample plen[b] = S.  (Given less, it softmaxes over the keys it has.)
+ *   The rows that exist get exactly the values of the padded call on the same data, bit for bit: keys in [klen, plen) carry
+ *   the -10000 bias in both layouts, keys in [plen, S) underflow to exactly 0 there and are exactly 0 here, and the key-tile
+ *   order is the same.  For dK / dV this holds when dO is zero at the padded call's rows in [plen, S) -- rows nothing reads
+ *   receive exactly that gradient -- because such a query row then adds exact zeros (D = 0, dS = 0, dO^T.P = 0).
+ *   Dropout is keyed by (b*nh + h, query position, key position) with Sp from S: the decisions of the padded call.
+ *   fbl_mha_bwd_rows takes the forward's output O (= ctx, stride ldo, a multiple of 8) instead of Dv as an input and writes
+ *   Dv fp32 [B,nh,S] = rowdot(dO, O) itself for the rows that exist (the arithmetic of fbl_attn_rowdot) in a first
+ *   launch, then runs the key-major and the query-major pass: three launches, enqueue-only. */
+int fbl_mha_fwd_rows(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const int32_t* mask,
+                     const int32_t* klen, const int32_t* border, const int32_t* row0, float scale, float p_drop, uint64_t seed,
+                     const uint64_t* seed_dev, void* ctx, int64_t ldo, float* lse, int B, int S, int nh, void* stream);
+
+int fbl_mha_bwd_rows(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* dO,
+                     int64_t lddo, const void* O, int64_t ldo, const int32_t* mask, const int32_t* klen, const int32_t* border,
+                     const int32_t* row0, const float* lse, float* Dv, float scale, float p_drop, uint64_t seed,
+                     const uint64_t* seed_dev, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, int B, int S,
+                     int nh, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
