@@ -34,7 +34,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import lib as L
-from .engine import BF16, F32, Engine, NormRef, Packing, Run, Stream, _ru, _StepFn
+from .engine import BF16, F32, Engine, NormRef, Packing, Run, Stream, _ru, _StepFn, check_logit_rows
 
 
 @dataclass
@@ -246,6 +246,11 @@ class BertEngine:
             fl = torch.cat([torch.full((B, T), -100, dtype=torch.long, device=self.dev), labels], 1) if use_video else labels
             full_labels = fl.contiguous().view(-1)
             rows_labelled = torch.nonzero(full_labels != -100).view(-1)
+        if logit_rows is not None:
+            if labels is not None:
+                raise RuntimeError("logit_rows cannot be combined with labels (the loss of a labelled call lives on its own rows)")
+            if need_grad:  # duplicates would race in the backward's scatter-add; refused before anything is queued
+                check_logit_rows(logit_rows, B * S)
         # packed rows (opt-in): only for calls whose outputs live on selected rows; the layout is a function of the input,
         # read back before anything is queued (as Engine.run does it)
         pk = None
@@ -269,9 +274,7 @@ class BertEngine:
                 run.label_rows = rows_labelled
                 run.rows = pk.inv[rows_labelled]
         use_ans = bool(m.n_ans) and not mlm
-        if logit_rows is not None:
-            if need_grad or labels is not None:
-                raise RuntimeError("logit_rows is an inference-time option (no labels, no gradient bookkeeping)")
+        if logit_rows is not None:  # the head runs on these rows only; with gradients its backward does too
             run.logit_rows = logit_rows.to(self.dev).to(torch.int32).contiguous().view(-1)
             if pk is not None:
                 run.logit_rows = pk.inv[run.logit_rows.long()].to(torch.int32)
@@ -342,7 +345,9 @@ class BertEngine:
             hin = torch.empty(rows_only.numel(), H, dtype=BF16, device=dev)
             if rows_only.numel():
                 L.gather_rows_bf16(x.bf16, rows_only, hin)
-            _, hl = self._head_stage(run, hin)
+            hp, hl = self._head_stage(run, hin)
+            if run.save:  # row-compact: what the head backward of exactly these rows reads
+                run.head_pre, run.head_norm = hp, hl.norm
             logits = torch.empty(rows_only.numel(), ldv, dtype=F32, device=dev)
             L.gemm(hl.bf16, table, bias=bias, out_f32=logits, N=Vout)
             run.logits = logits
@@ -435,6 +440,8 @@ class BertEngine:
         if attach:
             self.attach_grads()
         red = self.reducer  # data parallel: told when a stage's bucket is final, where collectives may start, when the step ends
+        if run.logit_rows is not None and run.logit_rows.numel() == 0 and red is None:
+            return  # no row was asked for: every gradient is exactly zero, nothing is launched (a reducer still needs its buckets)
         dx = L.zeros(N, H, dtype=F32, device=dev)
         Vout = run.Vout
         Vp = _ru(Vout, 64)
@@ -445,7 +452,13 @@ class BertEngine:
             ar = torch.arange(R, dtype=torch.int32, device=dev)
             L.ce_bwd_rows(run.logits_c, run.labels_c, ar, Vout, Vp, run.row_lse, run.loss_acc, gs, dlog)
             dx = self._head_bwd(run, run.rows_i32, dlog, dx)
-        if glogits is not None:
+        if glogits is not None and run.logit_rows is not None:  # the requested rows only (distinct: check_logit_rows)
+            R = run.logit_rows.numel()
+            if R:
+                dlog = torch.zeros(R, Vp, dtype=BF16, device=dev)
+                dlog[:, :Vout].copy_(glogits.reshape(R, Vout))
+                dx = self._head_bwd(run, run.logit_rows, dlog, dx, compact=True)
+        elif glogits is not None:
             gl = glogits.reshape(B * S, Vout)
             if pk is not None:  # (gradients handed in at positions without a row have nothing to flow into)
                 gl = gl.index_select(0, pk.sel)
@@ -473,8 +486,9 @@ class BertEngine:
             red.ready("emb")
             red.finish()
 
-    def _head_bwd(self, run, rows, dlog, dx):
-        """dx[rows] += d/d(head input) for the bf16 logit gradients dlog [R, Vp] of those rows (rows None: every row); returns dx"""
+    def _head_bwd(self, run, rows, dlog, dx, compact=False):
+        """dx[rows] += d/d(head input) for the bf16 logit gradients dlog [R, Vp] of those rows (rows None: every row); returns dx.
+        compact: the forward ran the head on exactly these rows (logit_rows), so what it saved is already [R, .]."""
         H, dev = self.H, self.dev
         R = dlog.shape[0]
         tableT = self.AnsTb if run.use_ans else self.ETb
@@ -485,7 +499,7 @@ class BertEngine:
         else:
             L.gemm(dlog, tableT, out_f32=dhl, N=H, splitk=max(2, min(16, Vp // 8192)), ws=self.sk_ws)
         hn = run.head_norm
-        if rows is None:
+        if rows is None or compact:
             sub, pre = hn, run.head_pre
         else:
             rl = rows.long()

@@ -28,6 +28,22 @@ def _ru(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+def check_logit_rows(logit_rows: torch.Tensor, n_grid: int) -> None:
+    """`logit_rows` of a call that keeps gradient bookkeeping: the backward adds the head's input gradient into the rows with
+    a plain += (fbl_scatter_rows_f32), so an index given twice would race and one outside the [B, S] grid would write out
+    of bounds.  Both are refused here, on the host, before anything is queued (one read of an input, like the label count)."""
+    r = logit_rows.reshape(-1)
+    if r.numel() == 0:
+        return
+    s = torch.sort(r.long()).values
+    dup = (s[1:] == s[:-1]).any() if s.numel() > 1 else torch.zeros((), dtype=torch.bool, device=s.device)
+    lo, hi, dup = torch.stack([s[0], s[-1], dup.long()]).tolist()
+    if lo < 0 or hi >= n_grid:
+        raise ValueError(f"logit_rows must index the [B, S] token grid: 0 <= row < {n_grid} (got {lo} .. {hi})")
+    if dup:
+        raise ValueError("logit_rows holds an index more than once: with gradients every requested row must be distinct")
+
+
 @dataclass
 class NormRef:
     """A tensor given in LayerNorm-normalised form (see module docstring)."""
@@ -492,6 +508,11 @@ class Engine:
             # The labelled rows are a function of the INPUT only: find them before anything is queued, so the host
             # synchronisation inside nonzero() waits for the previous step at most, never for this forward.
             rows_labelled = torch.nonzero(full_labels != -100).view(-1)
+        if logit_rows is not None:
+            if full_labels is not None:
+                raise RuntimeError("logit_rows cannot be combined with labels (the loss of a labelled call lives on its own rows)")
+            if need_grad:  # (the no-grad path only gathers: it stays as permissive as it was)
+                check_logit_rows(logit_rows, B * S)
         # Packed rows (opt-in, frozenbilm_amd extension): drop the trailing padding rows of every sample.  Only for calls
         # whose outputs live on selected rows (a loss, logit_rows); like the label rows, the layout is a function of the
         # INPUT, read back before anything is queued.
@@ -518,16 +539,14 @@ class Engine:
             run.rows = pk.inv[rows_labelled]
         self._refresh_if_stale(need_grad)  # bf16 operands / composed adapter rows of the trainable parameters
         use_ans = bool(m.n_ans) and not mlm
-        if logit_rows is not None:
-            if need_grad or full_labels is not None:
-                raise RuntimeError("logit_rows is an inference-time option (no labels, no gradient bookkeeping)")
+        if logit_rows is not None:  # the head runs on these rows only; with gradients its backward does too (_backward)
             run.logit_rows = logit_rows.to(self.dev).to(torch.int32).contiguous().view(-1)
             if pk is not None:
                 run.logit_rows = pk.inv[run.logit_rows.long()].to(torch.int32)
         with L.seed_word(run.seed_word):
             logits, loss_t = self._forward(run, input_ids.contiguous(), video, use_ans, want_hidden or want_attn)
         Vout = self.n_ans if use_ans else self.V
-        if logit_rows is not None:  # (an inference call: neither of the loss / autograd branches below applies)
+        if logit_rows is not None:  # [R, Vout]; under autograd the node below carries them (fine-tuning on the [MASK] rows)
             res = {"logits": logits[:, :Vout], "loss": None, "run": run}
         else:  # (packed rows: `logits` is the [B*S, V] grid tensor here too -- allocated in _forward, filled on access)
             res = {"logits": logits.view(B, S, -1)[:, :, :Vout] if logits is not None else None, "loss": None, "run": run}
@@ -828,8 +847,8 @@ class Engine:
         if loss_rows:
             run.head_in_all = q.bf16
             rows_only = run.rows.to(torch.int32)
-        if rows_only is not None:  # inference on selected token rows (the [MASK] rows of videoqa.py:164-168 / mc.py:166-170)
-            N = rows_only.numel()
+        if rows_only is not None:  # selected token rows only (the [MASK] rows of videoqa.py:66-69,164-168 / mc.py:166-170);
+            N = rows_only.numel()    # what the head saves for its backward (head_pre, head_norm) is then row-compact too
             hin = torch.empty(N, H, dtype=BF16, device=dev)
             if N:
                 L.gather_rows_bf16(q.bf16, rows_only, hin)
@@ -1128,9 +1147,10 @@ class Engine:
             run.pos_chain.add(st, sv.seed_pos)
         return dqkv
 
-    def _head_bwd(self, run, rows, dlog, dq, all_rows=False):
+    def _head_bwd(self, run, rows, dlog, dq, all_rows=False, compact=False):
         """Backward of the prediction head for the rows `rows` (int32 indices into the N token rows) given their bf16
-        logit gradients dlog [R, Vp]: dq[rows] += d/d(head input).  Head LayerNorm gradients are accumulated."""
+        logit gradients dlog [R, Vp]: dq[rows] += d/d(head input).  Head LayerNorm gradients are accumulated.
+        compact: the forward ran the head on exactly these rows (logit_rows), so what it saved is already [R, .]."""
         H, dev = self.H, self.dev
         R, Vp = dlog.shape
         Vout = run.Vout
@@ -1144,12 +1164,15 @@ class Engine:
             L.gemm(dlog, tableT, out_f32=dhl)
         else:  # few rows, long K -> split-K so the grid covers the chip (accumulates into zeros)
             L.gemm(dlog, tableT, out_f32=dhl, splitk=max(2, min(16, Vp // 8192)), ws=self.sk_ws)
-        rl = rows.long()
         hn = run.head_norm
-        sub = NormRef(hn.t[rl].contiguous(), hn.stats[rl].contiguous(), hn.gamma, hn.beta)
+        if compact:
+            sub, pre = hn, run.head_pre
+        else:
+            rl = rows.long()
+            sub, pre = NormRef(hn.t[rl].contiguous(), hn.stats[rl].contiguous(), hn.gamma, hn.beta), run.head_pre[rl].contiguous()
         dt, _ = self._ln_bwd("lm_predictions.lm_head.LayerNorm", dhl, sub, 0.0, 0, want_dy_bf16=False)
         dpre = torch.empty(R, H, dtype=BF16, device=dev)
-        L.dropout_gelu_bwd(dt, run.head_pre[rl].contiguous(), 0.0, 0, out_bf16=dpre)
+        L.dropout_gelu_bwd(dt, pre, 0.0, 0, out_bf16=dpre)
         dqr = torch.empty(R, H, dtype=F32, device=dev)
         L.gemm(dpre, self.WhT, out_f32=dqr)
         if all_rows:
@@ -1175,6 +1198,8 @@ class Engine:
         if attach:
             self.attach_grads()
         reducer = self.reducer
+        if run.logit_rows is not None and run.logit_rows.numel() == 0 and reducer is None:
+            return  # no row was asked for: every gradient is exactly zero, nothing is launched (a reducer still needs its buckets)
 
         red = _Ready(self, run, reducer) if reducer is not None else None
         run.dw_pending, run.dw_ready_keys, run.dw_count = [], [], 0
@@ -1193,8 +1218,18 @@ class Engine:
                 L.ce_bwd_rows(run.logits_c, run.labels_c, ar, Vout, Vp, run.row_lse, run.loss_acc, gs, dlog)
                 self._head_bwd(run, rows, dlog, dq)
                 del dlog
+        # ---- gradient handed in on the logits of the requested rows (logit_rows): the head backward on those R rows only,
+        # scatter-added into the zeroed dq at their activation rows (distinct: check_logit_rows)
+        if glogits is not None and run.logit_rows is not None:
+            rows = run.logit_rows
+            R = rows.numel()
+            if R > 0:
+                dlog = torch.zeros(R, Vp, dtype=BF16, device=dev) if Vp != Vout else torch.empty(R, Vp, dtype=BF16, device=dev)
+                dlog[:, :Vout].copy_(glogits.reshape(R, Vout))
+                self._head_bwd(run, rows, dlog, dq, compact=True)
+                del dlog
         # ---- gradient handed in on the logits themselves (downstream losses): every token row
-        if glogits is not None:
+        elif glogits is not None:
             gl = glogits.reshape(B * S, Vout)
             if pk is not None:  # (gradients handed in at positions without a row have nothing to flow into)
                 gl = gl.index_select(0, pk.sel)
@@ -1365,7 +1400,7 @@ class Run:
     labels: torch.Tensor = None                    # int64 [B*S] on the padded grid (-100: no label), or None
     rows: torch.Tensor = None                      # int64: the labelled activation rows
     label_rows: Optional[torch.Tensor] = None      # packed rows only: the same rows on the padded grid (where `labels` live)
-    logit_rows: Optional[torch.Tensor] = None      # int32: inference on these activation rows only
+    logit_rows: Optional[torch.Tensor] = None      # int32: the head (and, with gradients, its backward) on these activation rows only
     want_attn: bool = False                        # output_attentions=True
     seed_word: Optional[torch.Tensor] = None       # device word added to every dropout seed of this pass (see Engine.run)
     pk: Optional["Packing"] = None                 # packed-row layout of this pass (model.packed_rows) or None: the padded [B, S] grid
@@ -1428,7 +1463,8 @@ class Run:
 
 class _StepFn(torch.autograd.Function):
     """Single autograd node for the whole model: forward already ran; backward runs Engine.backward which writes the
-    gradients straight into the flat grad buffer (p.grad views), so autograd itself accumulates nothing."""
+    gradients straight into the flat grad buffer (p.grad views), so autograd itself accumulates nothing.  logits_t is the
+    [B, S, Vout] grid or, for a `logit_rows` call, the [R, Vout] rows; glogits arrives in the same shape."""
 
     @staticmethod
     def forward(ctx, engine, run, loss_t, logits_t, *params):

@@ -61,6 +61,8 @@ def mc_loss(scores, gt, n_choices):
 
 def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, args, max_norm: float = 0):
     model.train()
+    if getattr(args, "packed_rows", False) and hasattr(model, "packed_rows"):
+        model.packed_rows = True  # ragged batches without the padding rows behind each sample's last token (implies the rows route)
     run = EpochRunner(data_loader, args, "Epoch: [{}]".format(epoch), epoch)
     # several forwards feed one step: under data parallelism the gradient exchange waits for the last backward pass
     reducer = getattr(model.engine(), "reducer", None) if hasattr(model, "engine") else None

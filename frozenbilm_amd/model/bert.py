@@ -193,7 +193,8 @@ class BertForMaskedLM(nn.Module):
                 position_ids=None, head_mask=None, inputs_embeds=None, encoder_hidden_states=None, encoder_attention_mask=None,
                 labels=None, output_attentions=None, output_hidden_states=None, return_dict=None, mlm=False, logit_rows=None):
         """Reference keywords (model/bert.py:790-810) plus ``logit_rows`` -- flat row indices b*S + s of the [B, S] token grid
-        (S = video slots + text): at inference the head then runs on those rows only and ``logits`` is [len(logit_rows), V]."""
+        (S = video slots + text): the head then runs on those rows only and ``logits`` is [len(logit_rows), V]; under autograd
+        they are differentiable (distinct rows inside the grid, no ``labels`` next to them)."""
         if input_ids is not None and inputs_embeds is not None:
             raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
         if inputs_embeds is not None:

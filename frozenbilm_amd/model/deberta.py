@@ -457,9 +457,11 @@ class DebertaV2ForMaskedLM(nn.Module):
         logit_rows=None,
     ):
         """Reference signature (model/deberta.py:1414-1427) plus two keyword extensions: ``output_hidden_states`` and
-        ``logit_rows`` -- int tensor of flat row indices b*S + s into the [B, S] token grid (S = video slots + text): at
-        inference the prediction head then runs on those rows only and ``logits`` is [len(logit_rows), V] (the downstream
-        loops read one [MASK] row per sample: videoqa.py:164-168, mc.py:166-170)."""
+        ``logit_rows`` -- int tensor of flat row indices b*S + s into the [B, S] token grid (S = video slots + text): the
+        prediction head then runs on those rows only and ``logits`` is [len(logit_rows), V] (the downstream loops read one
+        [MASK] row per sample: videoqa.py:66-69,164-168, mc.py:166-170).  Under autograd these logits are differentiable and
+        the head's backward runs on the same rows; the indices must then be distinct and inside the grid (ValueError), and
+        ``labels`` cannot be given next to them."""
         if input_ids is not None and inputs_embeds is not None:
             raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
         if input_ids is None:

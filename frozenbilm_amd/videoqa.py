@@ -31,9 +31,12 @@ def mask_rows(encoded_ids, tokenizer, args, device):
 
 def answer_logits(model, tokenizer, encoded_ids, args, **feed):
     """Logits of the [MASK] rows, [n_mask, n_ans].  Without gradients the HIP model runs its prediction head on those rows
-    only (``logit_rows``); any other model -- or a training pass -- takes the reference's route: full logits, then
-    the row selection of videoqa.py:164-168."""
-    if hasattr(model, "engine") and not torch.is_grad_enabled():
+    only (``logit_rows``).  A training pass does the same -- head forward and backward on the [MASK] rows -- when the caller
+    opts in with ``args.train_logit_rows`` or ``args.packed_rows`` (packing needs the rows); any other model, and a training
+    pass without the opt-in, takes the reference's route: full logits, then the row selection of videoqa.py:164-168."""
+    rows_route = (not torch.is_grad_enabled() or getattr(args, "train_logit_rows", False)
+                  or getattr(args, "packed_rows", False))
+    if hasattr(model, "engine") and rows_route:
         rows = mask_rows(encoded_ids, tokenizer, args, feed["input_ids"].device)
         return model(logit_rows=rows, **feed)["logits"]
     return mask_row_logits(model(**feed)["logits"], encoded_ids, tokenizer, args)
@@ -68,14 +71,15 @@ def topk_agreement(logits, answer_id, dataset_name, thresholds):
 
 def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, dataset_name, args, max_norm: float = 0):
     model.train()
+    if getattr(args, "packed_rows", False) and hasattr(model, "packed_rows"):
+        model.packed_rows = True  # ragged batches without the padding rows behind each sample's last token (implies the rows route)
     run = EpochRunner(data_loader, args, "Epoch: [{}]".format(epoch), epoch)
     log = LossLog(run, "cls_loss", delayed=getattr(args, "delayed_loss_check", False), reducer=getattr(model, "_reducer", None))
     for i_batch, batch_dict in run:
         video, video_mask = video_inputs(batch_dict, device)
         encoded = tokenize(tokenizer, batch_dict["text"], args)
-        output = model(video=video, video_mask=video_mask, input_ids=encoded["input_ids"].to(device),
-                       attention_mask=encoded["attention_mask"].to(device))
-        logits = mask_row_logits(output["logits"], encoded["input_ids"], tokenizer, args)
+        logits = answer_logits(model, tokenizer, encoded["input_ids"], args, video=video, video_mask=video_mask,
+                               input_ids=encoded["input_ids"].to(device), attention_mask=encoded["attention_mask"].to(device))
         loss = vqa_loss(logits, batch_dict["answer_id"].to(device), dataset_name)
         logged_step(log, loss, optimizer, model, max_norm)
         run.schedule(optimizer, i_batch)

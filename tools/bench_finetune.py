@@ -1,0 +1,140 @@
+"""Device-event timings of a fine-tuning step at the xlarge dimensions (one JSON object).
+
+    python tools/bench_finetune.py [--steps K] [--warmup W] [--layers N]
+
+Two workloads, each a full training step -- forward, the caller's loss on the [MASK]-row logits, backward, clipped FusedAdam
+-- in train mode with every dropout site live, through `videoqa.answer_logits` (the call both fine-tuning loops make):
+
+  videoqa  B = 32 questions, 10 video slots, ragged short questions (8 .. 64 tokens, one [MASK] each), n_ans = 1000,
+           cross-entropy on the answer logits (videoqa.py:66-83)
+  mc       B = 8 questions x C = 4 candidates in ONE forward of 32 samples (mc.candidate_scores), ragged speech context up
+           to S = 512, the 2-way answer head, balanced BCE on softmax[:, 0] (mc.py:64-92)
+
+Three legs per workload:
+
+  full         the default route: full [B, S, n_ans] logits, head forward and backward on every token row
+  rows         args.train_logit_rows: head forward and backward on the [MASK] rows only (logit_rows under autograd)
+  rows_packed  args.packed_rows: the same on packed rows (model.packed_rows)
+
+The legs alternate inside one process (one model, one optimizer; every leg is a real update); per leg the median and the
+10th / 90th percentile over the timed iterations, and the share of token rows that exist on the packed layout.
+"""
+import argparse
+import json
+import os
+import sys
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn.functional as F
+
+from frozenbilm_amd import mc as P_mc
+from frozenbilm_amd import videoqa as P_vqa
+from frozenbilm_amd.model import DebertaV2Config, DebertaV2ForMaskedLM
+from frozenbilm_amd.optim import FusedAdam
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=20, help="timed iterations per leg (at least 20 for the record)")
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--layers", type=int, default=0, help="encoder layers (0: the xlarge model's 24)")
+ap.add_argument("--only", choices=["videoqa", "mc"], default=None)
+a = ap.parse_args()
+dev = torch.device("cuda")
+T, FEAT, MASK = 10, 768, 128000
+
+
+class Tok:
+    mask_token_id, pad_token_id, sep_token_id = MASK, 0, 2
+
+
+def texts(n, lo, hi, seed):
+    """n ragged token rows padded to the longest (which is `hi` long), exactly one [MASK] inside each"""
+    g = torch.Generator().manual_seed(seed)
+    tlen = torch.randint(lo, hi + 1, (n,), generator=g)
+    tlen[-1] = hi
+    ids = torch.randint(5, 127000, (n, hi), generator=g) * (torch.arange(hi)[None] < tlen[:, None])
+    ids[torch.arange(n), torch.stack([torch.randint(1, int(t), (1,), generator=g) for t in tlen]).view(-1)] = MASK
+    return ids, tlen
+
+
+def alternate_stats(legs, n, warm):
+    """per leg {median, p10, p90} in ms; the legs run in turn inside each iteration"""
+    ev = {k: [] for k in legs}
+    for it in range(warm + n):
+        for k, f in legs.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            f()
+            e.record()
+            if it >= warm:
+                ev[k].append((s, e))
+    torch.cuda.synchronize()
+    res = {}
+    for k, v in ev.items():
+        t = sorted(s.elapsed_time(e) for s, e in v)
+        pick = lambda q: round(t[min(len(t) - 1, int(q * len(t)))], 2)
+        res[k] = {"median": pick(0.5), "p10": pick(0.1), "p90": pick(0.9), "n": len(t)}
+    return res
+
+
+def workload(name):
+    cfg = DebertaV2Config()
+    if a.layers:
+        cfg.num_hidden_layers = a.layers
+    n_ans = 1000 if name == "videoqa" else 2
+    torch.manual_seed(0)
+    m = DebertaV2ForMaskedLM(cfg, max_feats=T, features_dim=FEAT, ds_factor_attn=8, ds_factor_ff=8, dropout=0.1, n_ans=n_ans)
+    m.to(dev).eval()
+    g = torch.Generator().manual_seed(1)
+    a2tok = torch.randint(5, cfg.vocab_size, (n_ans, 5), generator=g)
+    m.set_answer_embeddings((a2tok * (torch.arange(5)[None] < torch.randint(1, 6, (n_ans, 1), generator=g))).to(dev))
+    m.train()
+    opt = FusedAdam(m, lr=1e-5)
+    if name == "videoqa":
+        B, C = 32, 1
+        ids, tlen = texts(B, 8, 64, seed=2)
+        target = torch.randint(0, n_ans, (B,), generator=g).to(dev)
+    else:
+        B, C = 8, 4
+        ids, tlen = texts(C * B, 64, 502, seed=3)
+        target = torch.randint(0, C, (B,), generator=g).to(dev)
+    n = ids.shape[0]
+    S = T + ids.shape[1]
+    vlen = torch.randint(1, T + 1, (B,), generator=g)
+    video = torch.randn(B, T, FEAT, generator=g).half().float().repeat(C, 1, 1).to(dev)
+    vmask = (torch.arange(T)[None] < vlen[:, None]).long().repeat(C, 1).to(dev)
+    feed = dict(video=video, video_mask=vmask, input_ids=ids.to(dev), attention_mask=(ids != 0).long().to(dev))
+    rows_packed = int((tlen + T).sum())  # every sample keeps its video slots and its text up to the last token
+
+    def step(**opt_in):
+        args = types.SimpleNamespace(max_feats=T, use_video=True, **opt_in)
+        m.packed_rows = bool(opt_in.get("packed_rows"))
+        opt.zero_grad()
+        logits = P_vqa.answer_logits(m, Tok, ids, args, **feed)
+        if name == "videoqa":
+            loss = F.cross_entropy(logits, target)
+        else:
+            loss = P_mc.mc_loss(logits.softmax(-1)[:, 0].view(C, B).t(), target, C)
+        loss.backward()
+        opt.step(clip_max_norm=0.1)
+
+    legs = {"full": lambda: step(), "rows": lambda: step(train_logit_rows=True), "rows_packed": lambda: step(packed_rows=True)}
+    res = {"shape": dict(samples=n, S=S, T=T, n_ans=n_ans, candidates=C, layers=cfg.num_hidden_layers, mask_rows=n),
+           "rows": {"padded": n * S, "packed": rows_packed, "share": round(rows_packed / (n * S), 3)},
+           "step_ms": alternate_stats(legs, a.steps, a.warmup)}
+    full = res["step_ms"]["full"]["median"]
+    res["speedup_vs_full"] = {k: round(full / v["median"], 3) for k, v in res["step_ms"].items() if k != "full"}
+    del m, opt
+    torch.cuda.empty_cache()
+    return res
+
+
+out = {"device": torch.cuda.get_device_name(0),
+       "method": "device events around forward + loss + backward + clipped FusedAdam, train mode (dropout live); the three legs "
+                 f"alternate inside one process; median, 10th and 90th percentile of {a.steps} timed iterations after {a.warmup} "
+                 "warm-up iterations"}
+for w in ("videoqa", "mc"):
+    if a.only in (None, w):
+        out[w] = workload(w)
+print(json.dumps(out))
