@@ -162,6 +162,13 @@ class PosChain:
     seeds: list = field(default_factory=list)   # seed of each execution's position dropout
     klen: Optional[torch.Tensor] = None         # the same for every execution of a step
     row0: Optional[torch.Tensor] = None
+    # Executions that form their table gradients themselves (the decoder on selected rows, engine._attn_bwd_qrows) are the FIRST
+    # of the chain; they write into dbuf = (dPK, dPQ) fp32 [n_exec, nh, rcnt, 64], the buffers fbl_attn_pos_grad fills for the rest
+    n_formed: int = 0
+    n_exec: int = 0
+    nh: int = 0
+    dev: Optional[torch.device] = None
+    dbuf: Optional[tuple] = None
 
     def add(self, st, seed_pos):
         """st: the state disent_attn_bwd(defer_pos=True) returned for one execution"""
@@ -169,11 +176,22 @@ class PosChain:
         self.seeds.append(seed_pos)
         self.klen, self.row0 = st["klen"], st["row0"]
 
+    def formed_slot(self):
+        """(dPK, dPQ) fp32 [nh, rcnt, 64] of the next execution that forms its table gradients itself"""
+        assert not self.dS and self.n_exec > self.n_formed, "executions with formed table gradients come first"
+        if self.dbuf is None:
+            self.dbuf = tuple(torch.empty(self.n_exec, self.nh, self.rcnt, 64, dtype=F32, device=self.dev) for _ in range(2))
+        return self.dbuf[0][self.n_formed], self.dbuf[1][self.n_formed]
+
+    def add_formed(self, seed_pos):
+        self.n_formed += 1
+        self.seeds.append(seed_pos)
+
 
 def pos_chain_buffers(eng, run):
     """an empty PosChain for the backward of `run`"""
     rmin, rcnt = _relidx_range(run.S, eng.cfg)
-    return PosChain(rmin=rmin, rcnt=rcnt, B=run.B, S=run.S, Sp=(run.S + 63) // 64 * 64)
+    return PosChain(rmin=rmin, rcnt=rcnt, B=run.B, S=run.S, Sp=(run.S + 63) // 64 * 64, nh=eng.nh, dev=eng.dev)
 
 
 def pos_table_grads_batched(eng, run, pc: PosChain):
@@ -194,8 +212,14 @@ def pos_table_grads_batched(eng, run, pc: PosChain):
     dpb = torch.empty(E, rcnt, 2 * H, dtype=BF16, device=dev)
     dlo, dcnt, cmax = _delta_ranges(pc.S, eng.cfg, dev, limit=None)
     for neg, X, Y, col0 in ((0, pc.dS, pc.q, H), (1, pc.dST, pc.k, 0)):
-        d = torch.empty(E, nh, rcnt, 64, dtype=F32, device=dev)
-        L.attn_pos_grad(neg, X, Y, dlo, dcnt, cmax, d, B, pc.S, Sp, nh, rcnt, klen=pc.klen, row0=pc.row0)
+        nf = pc.n_formed
+        if pc.dbuf is not None:  # the first nf executions have written their tables already
+            assert pc.n_exec == E, (pc.n_exec, E)
+            d = pc.dbuf[neg]
+        else:
+            d = torch.empty(E, nh, rcnt, 64, dtype=F32, device=dev)
+        if X:
+            L.attn_pos_grad(neg, X, Y, dlo, dcnt, cmax, d[nf:], B, pc.S, Sp, nh, rcnt, klen=pc.klen, row0=pc.row0)
         # [e, h, r, 64] fp32 -> [e, r, h*64 + .] bf16, into this table's column block
         L.heads_to_rows_bf16(d, dpb[:, :, col0:col0 + H])
     tmp = torch.empty(E, rcnt, H, dtype=F32, device=dev)

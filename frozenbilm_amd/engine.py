@@ -534,6 +534,11 @@ class Engine:
         if want_attn and train and run.p_att > 0:
             raise NotImplementedError("output_attentions=True is served in eval mode (the probabilities of a training forward "
                                       "carry the attention dropout mask, which the fused kernel regenerates instead of storing)")
+        # Decoder on the selected rows (opt-in `model.decoder_rows`): both enhanced-mask-decoder passes, the head and their
+        # backward run on the labelled rows / the logit_rows only; calls that need every row keep the full decoder.
+        if (getattr(m, "decoder_rows", False) and not want_attn and not want_hidden and not self.eager_logits
+                and (full_labels is not None or logit_rows is not None) and not torch.cuda.is_current_stream_capturing()):
+            run.dec_grid = (rows_labelled if full_labels is not None else logit_rows.to(self.dev).long().view(-1))
         if pk is not None and full_labels is not None:  # the head works on packed rows; the labels are looked up on the grid
             run.label_rows = rows_labelled
             run.rows = pk.inv[rows_labelled]
@@ -814,6 +819,8 @@ class Engine:
             hs.append(x)
         # ---- enhanced mask decoder (:1382-1412): q0 = pos_emb + hs[-2]; two passes of the last layer
         kv = hs[nL - 1]
+        if run.dec_grid is not None:  # model.decoder_rows: q0 and everything behind it on the selected rows only
+            return self._decoder_rows_fwd(run, kv, Rb, use_ans)
         q32 = torch.empty(N, H, dtype=F32, device=dev)
         qfull = torch.empty(N + self.span2, H, dtype=BF16, device=dev)
         if pk is None:
@@ -894,11 +901,121 @@ class Engine:
         run.logits = logits
         return logits, None
 
+    def _decoder_rows_fwd(self, run, kv: Stream, Rb, use_ans):
+        """The enhanced mask decoder, the head and the loss on the selected rows only (model.decoder_rows).  A decoder row
+        depends on its own query row and on all of hs[-2] (both passes take keys and values from it; everything behind the
+        attention is row-wise), so this is exact.  K|V of hs[-2] are projected once for both passes; per pass the query
+        projection runs on the R compact rows and [PQ|PK] on the position table (its own position-dropout seed), the attention
+        is fbl_disent_attn_fwd_qrows, and dense / adapter / LayerNorm / FFN run at N = R.  Row-keyed dropout sites key by the
+        compact row.  The order of run.next_seed() calls is that of _layer_fwd."""
+        from .row_plan import plan_query_rows
+
+        H, I, nh, dev, nL = self.H, self.I, self.nh, self.dev, self.nL
+        B, S, N = run.B, run.S, run.N
+        li = nL - 1
+        W = self.Lw[li]
+        pk = run.pk
+        pl = plan_query_rows(run.dec_grid, B, S, inv=pk.inv if pk is not None else None)
+        run.dec_plan = pl
+        R = pl.R
+        Sp = _ru(S, 64)
+        a1, a2 = self.sites[li]
+        p = f"deberta.encoder.layer.{li}"
+        q = None
+        if R:
+            # q0 = pos_emb[pos] + hs[-2][rows], materialised for the R selected rows only
+            n_ = kv.norm
+            if n_ is not None:
+                qc32 = torch.empty(R, H, dtype=F32, device=dev)
+                rm = n_.rowmask.index_select(0, pl.krows) if n_.rowmask is not None else None
+                L.ln_materialize(n_.t.index_select(0, pl.krows), n_.stats.index_select(0, pl.krows), n_.gamma, n_.beta, rowmask=rm,
+                                 out_f32=qc32)
+            else:
+                qc32 = kv.plain.index_select(0, pl.krows)
+            qc32.add_(self.pos_emb.index_select(0, pl.rpos.long()))
+            q = Stream(bf16=qc32.to(BF16), plain=qc32)
+            kvp = torch.empty(N, 2 * H, dtype=BF16, device=dev)
+            L.gemm(kv.bf16, W["Wqkv"][H:], bias=W["bqkv"][H:], out_bf16=kvp)
+        for _ in range(2):
+            sv = LayerSave(li=li, emd=True)
+            if run.p_hid > 0:
+                sv.seed_pos = run.next_seed()
+            sv.seed_att = run.next_seed() if run.p_att > 0 else 0
+            if not R:  # nothing selected: no decoder work; the seeds of the remaining sites are drawn as the full route draws them
+                for on in (a1 is not None and run.p_ad > 0, run.p_hid > 0, a2 is not None and run.p_ad > 0, run.p_hid > 0):
+                    if on:
+                        run.next_seed()
+                continue
+            if run.p_hid > 0:
+                Rd = torch.empty(self.span2, H, dtype=BF16, device=dev)
+                L.dropout_f32(run.R32, run.p_hid, sv.seed_pos, out_bf16=Rd)
+            else:
+                Rd = Rb
+            infer = not run.save and run.p_hid == 0
+            if infer and getattr(self.m, "_weights_frozen", 0) > 0 and not self._no_pos_cache:
+                pqk = self._pos_proj_cached(li, W, Rb)
+            else:
+                pqk = torch.empty(self.span2, 2 * H, dtype=BF16, device=dev)
+                L.gemm(Rd, W["Wqkv"][: 2 * H], bias=W["bqkv"][: 2 * H], out_bf16=pqk)
+            qp = torch.empty(R, H, dtype=BF16, device=dev)
+            L.gemm(q.bf16, W["Wqkv"][:H], bias=W["bqkv"][:H], out_bf16=qp)
+            ctx = torch.empty(R, H, dtype=BF16, device=dev)
+            lse = torch.empty(nh, R, dtype=F32, device=dev)
+            L.disent_attn_fwd_qrows(qp, pl.rseg, pl.rpos, kvp[:, :H], kvp[:, H:], pqk[:, H:], pqk[:, :H], self.relidx(S), run.mask_i32,
+                                    run.klen, 1.0 / math.sqrt(64 * 3), ctx, lse, B, S, Sp, nh, self.span2, p_drop=run.p_att,
+                                    seed=sv.seed_att, row0=pk.row0 if pk is not None else None)
+            a, ob, z1, sv.seed_ad1, sv.seed_ln1 = self._dense_adapter_ln(
+                run, li, ctx, W["Wo"], W["bo"], a1, R, p + ".attention.output.LayerNorm", resid=q)
+            h = torch.empty(R, I, dtype=BF16, device=dev)
+            hpre = torch.empty(R, I, dtype=BF16, device=dev) if run.save else None
+            L.gemm(a.bf16, W["Wi"], bias=W["bi"], act=L.ACT_GELU_GRAD if run.save else L.ACT_GELU, out_bf16=h, out_pre=hpre)
+            out, fb, z2, sv.seed_ad2, sv.seed_ln2 = self._dense_adapter_ln(
+                run, li, h, W["Wd"], W["bd"], a2, R, p + ".output.LayerNorm", resid=Stream(bf16=a.bf16, norm=a.norm))
+            if run.save:
+                sv.qr = dict(q=qp, kv=kvp, pqk=pqk, ctx=ctx, lse=lse)
+                sv.ob, sv.z1, sv.ln1 = ob, z1, a.norm
+                sv.hpre, sv.fb, sv.z2, sv.ln2 = hpre, fb, z2, out.norm
+                run.layers.append(sv)
+            q = out
+        # ---- head on the compact rows directly (no gather)
+        if use_ans:
+            Vout, table, bias = self.n_ans, self.Ansb, self.ans_bias
+        else:
+            Vout, table, bias = self.V, self.Eb, self.head_bias
+        ldv = _ru(Vout, 64)
+        run.Vout, run.head_table, run.head_bias, run.ldv = Vout, table, bias, ldv
+        hin = q.bf16 if R else torch.empty(0, H, dtype=BF16, device=dev)
+        hp, hl = self._head_stage(run, hin, R)
+        run.head_pre, run.head_norm, run.head_ln_bf16 = hp, hl.norm, hl.bf16
+        lc = torch.empty(R, ldv, dtype=F32, device=dev)
+        if R:
+            L.gemm(hl.bf16, table, bias=bias, out_f32=lc, N=Vout)
+        if run.labels is None:  # logit_rows: [R, Vout] in the caller's order
+            run.logits = lc.index_select(0, pl.back)
+            return run.logits, None
+        # labelled call: nonzero() lists the rows in ascending order, which is the compact order
+        run.rows_i32 = run.rows.to(torch.int32)
+        run.loss_acc = L.zeros(2, dtype=F32, device=dev)
+        if R:
+            run.labels_c = run.labels[pl.grid].contiguous()
+            run.row_lse = torch.empty(R, dtype=F32, device=dev)
+            L.ce_fwd(lc, run.labels_c, Vout, run.row_lse, run.loss_acc)
+            run.logits_c = lc
+        loss_t = run.loss_acc[0] / run.loss_acc[1]
+        run.logits = torch.empty(B * S, ldv, dtype=F32, device=dev)  # the selected rows, zero elsewhere: filled on first access
+        run.logits_pending = True
+        return run.logits, loss_t
+
     def fill_logits(self, run):
         """Full [N, V] logits of a forward that only computed the labelled rows (see _forward); idempotent.  Writes into
         the storage of the tensor already handed out (and already wired into the autograd node), on the current stream."""
         if run.logits_pending:
             run.logits_pending = False
+            if run.dec_plan is not None:  # decoder on selected rows: only those rows have logits, the others read zero
+                run.logits.zero_()
+                if run.dec_plan.R:
+                    run.logits.index_copy_(0, run.dec_plan.grid, run.logits_c)
+                return
             hin_all = run.head_in_all
             if hin_all is not None:  # the forward ran the head on the labelled rows only: now on every row
                 _, hl = self._head_stage(run, hin_all, hin_all.shape[0])
@@ -1044,8 +1161,8 @@ class Engine:
                     rest.append(rec)
                 else:
                     names.add(nm)
-                    take.setdefault(A, []).append((nm, seg))
-            for A, recs in take.items():
+                    take.setdefault((A, getattr(seg[0], "shape", (None,))[0]), []).append((nm, seg))  # one launch takes one row count
+            for (A, _rows), recs in take.items():
                 L.adapter_bwd_dw([([seg], self.G[nm + ".up.weight"], self.G[nm + ".down.weight"], self.G[nm + ".down.bias"])
                                   for nm, seg in recs], A=A)
             kept = {id(r) for r in rest}
@@ -1093,7 +1210,7 @@ class Engine:
             # (25 launches a step).  A buffer returns to the pool when the parked gradient products that read its [dy | dz]
             # blocks have been enqueued (_dw_flush).  Captured steps and the immediate-launch route allocate as before.
             pooled = None
-            can_pool = not torch.cuda.is_current_stream_capturing() and a1.grouped
+            can_pool = not torch.cuda.is_current_stream_capturing() and a1.grouped and sv.qr is None  # (one pooled shape: N rows)
             if can_pool and self._dyz_shape != (N, Kf):  # a new batch shape (text padded to the longest sample): one pool, of
                 self._dyz_pool.clear()                           # the current shape only -- never one per shape seen
                 self._dyz_shape = (N, Kf)
@@ -1117,6 +1234,11 @@ class Engine:
             if a1 is not None:
                 do = self._adapter_bwd(run, a1, dy1, sv.z1, sv.ob, sv.seed_ad1)
             L.gemm(do, W["WoT"], out_bf16=dctx)
+        if sv.qr is not None:  # decoder on selected rows: dQ is compact, [dK | dV] covers every key row
+            dqc, dkv = self._attn_bwd_qrows(run, sv, dctx)
+            dq = torch.empty(N, H, dtype=F32, device=dev)
+            L.gemm(dqc, W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
+            return dq, dkv
         dqkv = self._attn_bwd(run, sv, dctx)
         if not sv.emd:
             dx = torch.empty(N, H, dtype=F32, device=dev)
@@ -1146,6 +1268,32 @@ class Engine:
         if run.pos_chain is not None:
             run.pos_chain.add(st, sv.seed_pos)
         return dqkv
+
+    def _attn_bwd_qrows(self, run, sv, dctx):
+        """Backward of the attention of one decoder execution on selected rows (fbl_disent_attn_bwd_qrows): returns dQ bf16
+        [R, H] and [dK | dV] bf16 [N, 2H]; its position-table gradients go straight onto the step's chain."""
+        from .attn_bwd import _relidx_range
+
+        B, S, H, nh, dev = run.B, run.S, self.H, self.nh, self.dev
+        pl, qr = run.dec_plan, sv.qr
+        R, Sp = pl.R, _ru(S, 64)
+        if self.reducer is not None:
+            self.reducer.window()
+        rmin, rcnt = _relidx_range(S, self.cfg)
+        dqc = torch.empty(R, H, dtype=BF16, device=dev)
+        dkv = torch.empty(run.N, 2 * H, dtype=BF16, device=dev)
+        # the table gradients are written straight into the chain's buffer of all executions; without a chain (nothing trainable
+        # behind the position table) the table pass is not launched
+        dpk, dpq = run.pos_chain.formed_slot() if run.pos_chain is not None else (None, None)
+        ws = torch.empty(L.disent_attn_bwd_qrows_ws_bytes(R, Sp, nh), dtype=torch.uint8, device=dev)
+        kvp, pqk = qr["kv"], qr["pqk"]
+        L.disent_attn_bwd_qrows(qr["q"], pl.rseg, pl.rpos, kvp[:, :H], kvp[:, H:], pqk[:, H:], pqk[:, :H], self.relidx(S), run.mask_i32,
+                                run.klen, dctx, qr["ctx"], qr["lse"], 1.0 / math.sqrt(64 * 3), dqc, dkv[:, :H], dkv[:, H:], dpk, dpq,
+                                rmin, rcnt, ws, B, S, Sp, nh, self.span2, p_drop=run.p_att, seed=sv.seed_att,
+                                row0=run.pk.row0 if run.pk is not None else None)
+        if run.pos_chain is not None:
+            run.pos_chain.add_formed(sv.seed_pos)
+        return dqc, dkv
 
     def _head_bwd(self, run, rows, dlog, dq, all_rows=False, compact=False):
         """Backward of the prediction head for the rows `rows` (int32 indices into the N token rows) given their bf16
@@ -1203,7 +1351,8 @@ class Engine:
 
         red = _Ready(self, run, reducer) if reducer is not None else None
         run.dw_pending, run.dw_ready_keys, run.dw_count = [], [], 0
-        dq = L.zeros(N, H, dtype=F32, device=dev)
+        dec = run.dec_plan  # decoder on selected rows: the head and the decoder work on the R compact rows
+        dq = L.zeros(dec.R if dec is not None else N, H, dtype=F32, device=dev)
         Vout = run.Vout
         Vp = _ru(Vout, 64)
         # ---- CE + head, on the labelled rows only (all other rows have exactly zero gradient)
@@ -1216,7 +1365,10 @@ class Engine:
                 gs = gloss.detach().to(F32) if (isinstance(gloss, torch.Tensor) and gloss.is_cuda) else float(gloss)
                 ar = torch.arange(R, dtype=torch.int32, device=dev)  # logits_c holds the labelled rows only
                 L.ce_bwd_rows(run.logits_c, run.labels_c, ar, Vout, Vp, run.row_lse, run.loss_acc, gs, dlog)
-                self._head_bwd(run, rows, dlog, dq)
+                if dec is not None:
+                    self._head_bwd(run, None, dlog, dq, all_rows=True, compact=True)
+                else:
+                    self._head_bwd(run, rows, dlog, dq)
                 del dlog
         # ---- gradient handed in on the logits of the requested rows (logit_rows): the head backward on those R rows only,
         # scatter-added into the zeroed dq at their activation rows (distinct: check_logit_rows)
@@ -1225,10 +1377,22 @@ class Engine:
             R = rows.numel()
             if R > 0:
                 dlog = torch.zeros(R, Vp, dtype=BF16, device=dev) if Vp != Vout else torch.empty(R, Vp, dtype=BF16, device=dev)
-                dlog[:, :Vout].copy_(glogits.reshape(R, Vout))
-                self._head_bwd(run, rows, dlog, dq, compact=True)
+                if dec is not None:  # the caller's order -> the compact order
+                    dlog[:, :Vout].copy_(glogits.reshape(R, Vout).index_select(0, dec.order))
+                    self._head_bwd(run, None, dlog, dq, all_rows=True, compact=True)
+                else:
+                    dlog[:, :Vout].copy_(glogits.reshape(R, Vout))
+                    self._head_bwd(run, rows, dlog, dq, compact=True)
                 del dlog
         # ---- gradient handed in on the logits themselves (downstream losses): every token row
+        elif glogits is not None and dec is not None:
+            # decoder on selected rows: out.logits holds the selected rows and constants (zero) elsewhere, so only the gradient
+            # handed in at those rows has anything to flow into -- taken at the grid rows in compact order
+            if dec.R:
+                dlog = torch.zeros(dec.R, Vp, dtype=BF16, device=dev) if Vp != Vout else torch.empty(dec.R, Vp, dtype=BF16, device=dev)
+                dlog[:, :Vout].copy_(glogits.reshape(B * S, Vout).index_select(0, dec.grid))
+                self._head_bwd(run, None, dlog, dq, all_rows=True, compact=True)
+                del dlog
         elif glogits is not None:
             gl = glogits.reshape(B * S, Vout)
             if pk is not None:  # (gradients handed in at positions without a row have nothing to flow into)
@@ -1248,13 +1412,25 @@ class Engine:
             from .attn_bwd import pos_chain_buffers
 
             run.pos_chain = pos_chain_buffers(self, run)
+            if dec is not None:  # the two decoder executions are the first of the chain also when nothing was selected (R = 0:
+                # they were not saved; zero tables keep the chain's order equal to the order of WposT_exec)
+                run.pos_chain.n_exec = len(run.layers) + (0 if dec.R else 2)
+                if not dec.R:
+                    for _ in range(2):
+                        dpk, dpq = run.pos_chain.formed_slot()
+                        dpk.zero_(); dpq.zero_()
+                        run.pos_chain.add_formed(0)
         # ---- EMD: two executions of the last layer, newest first
         layers = run.layers
         dkv_ops = []
-        for _ in range(2):
+        for _ in range(2 if dec is None or dec.R else 0):
             sv = layers.pop()
             dq, dkv_op = self._layer_bwd(run, sv, dq)
             dkv_ops.append(dkv_op)
+        if dec is not None:  # the query-stream gradient of the first pass lands on its rows of hs[-2] (distinct under gradients)
+            dqc, dq = dq, L.zeros(N, H, dtype=F32, device=dev)
+            if dec.R:
+                L.scatter_rows_f32(dqc, dec.krows.to(torch.int32), dq)
         # q0 = pos_emb + hs[-2]: the query-stream gradient flows into hs[-2] too, next to both passes' key/value-stream
         # gradients [dK | dV] . [Wk ; Wv] -- accumulated by the epilogues of those two GEMMs
         WkvT = self.Lw[self.nL - 1]["WqkvT"][:, H:]
@@ -1380,6 +1556,7 @@ class LayerSave:
     seed_ln2: int = 0
     psave: torch.Tensor = None
     msave: torch.Tensor = None
+    qr: Optional[dict] = None  # decoder on selected rows: compact q, the shared K|V, [PQ|PK], ctx, lse (see _decoder_rows_fwd)
 
 
 @dataclass
@@ -1419,6 +1596,8 @@ class Run:
     R32: Optional[torch.Tensor] = None             # fp32 [2*span, H]: that table, materialised for its dropout (training)
     # ---- layers
     layers: list = field(default_factory=list)     # LayerSave / BertLayerSave per execution that has a backward
+    dec_grid: Optional[torch.Tensor] = None        # model.decoder_rows: the selected rows on the padded grid, caller's order
+    dec_plan: Optional[object] = None              # ... their row_plan.QueryRowPlan
     emd_qkv: Optional[torch.Tensor] = None         # inference: Q|K|V of the first decoder pass, reused by the second
     attn_out: list = field(default_factory=list)   # want_attn: fp32 [B, nh, S, S] probabilities per encoder layer
     hidden_out: tuple = None                       # want_hidden: fp32 [B, S, H] per layer

@@ -89,6 +89,16 @@ MHA_SIGNATURES = {
                               _vp, _l, _vp, _l, _i, _i, _i, _vp]),
 }
 
+# the enhanced mask decoder's attention on selected query rows (include/fbl_qrows.h): a table of its own for the same reason
+QROWS_SIGNATURES = {
+    "fbl_disent_attn_fwd_qrows": (_i, [_vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp,
+                                       _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fbl_disent_attn_bwd_qrows_ws_bytes": (_l, [_i, _i, _i]),
+    "fbl_disent_attn_bwd_qrows": (_i, [_vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l,
+                                       _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp, _l, _i, _i, _i,
+                                       _i, _i, _vp]),
+}
+
 _LIB = None
 
 
@@ -103,7 +113,7 @@ def load(path: Optional[str] = None):
             f"{p} not found: the FrozenBiLM MI355X path needs its HIP library (python -m frozenbilm_amd.build); "
             "there is no CPU/eager fallback")
     lib = C.CDLL(p)
-    for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -560,6 +570,66 @@ def disent_attn_fwd(q, k, v, pk, pq, relidx, mask, scale, ctx, lse, B, S, Sp, nh
                                     _p(mask), _p(klen), _p(border), float(scale), float(p_drop), int(seed), _seed_dev(), _p(ctx), ldo,
                                     _p(lse), B, S, Sp, nh, span2, int(lin), _row0(row0, B, klen), _p(psave), _p(msave), _stream()),
          "fbl_disent_attn_fwd")
+
+
+def _qrows_common(q, rseg, rpos, k, v, pk, pq, relidx, mask, klen, B, S):
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (pk, "pk"), (pq, "pq")):
+        _req(t, torch.bfloat16, n)
+    for t, n in ((rseg, "rseg"), (rpos, "rpos"), (mask, "mask"), (klen, "klen")):
+        _req(t, torch.int32, n)
+        assert t.is_contiguous(), n
+    _req(relidx, torch.int16, "relidx")
+    R = q.shape[0]
+    assert rseg.numel() == B + 1 and rpos.numel() == R and relidx.numel() == 2 * S - 1 and mask.numel() == B * S and klen.numel() == B
+    ldp = _rows2d(pk, "pk")
+    assert _rows2d(pq, "pq") == ldp
+    return R, ldp
+
+
+def disent_attn_fwd_qrows(q, rseg, rpos, k, v, pk, pq, relidx, mask, klen, scale, ctx, lse, B, S, Sp, nh, span2, p_drop=0.0,
+                          seed=0, row0=None):
+    """the disentangled attention of the compact query rows q [R, .] (grouped by sample: rseg [B+1], positions rpos [R]) against
+    all key rows of their samples; ctx bf16 [R, .], lse fp32 [nh, R] (include/fbl_qrows.h)"""
+    R, ldp = _qrows_common(q, rseg, rpos, k, v, pk, pq, relidx, mask, klen, B, S)
+    _req(ctx, torch.bfloat16, "ctx"); _req(lse, torch.float32, "lse")
+    assert ctx.shape[0] == R and lse.is_contiguous() and lse.numel() == nh * R
+    if R == 0:  # nothing selected: no launch (an empty tensor has no address to pass)
+        return
+    _chk(load().fbl_disent_attn_fwd_qrows(_p(q), _rows2d(q, "q"), _p(rseg), _p(rpos), R, _p(k), _rows2d(k, "k"), _p(v),
+                                          _rows2d(v, "v"), _p(pk), _p(pq), ldp, _p(relidx), _p(mask), _p(klen),
+                                          _row0(row0, B, klen), float(scale), float(p_drop), int(seed), _seed_dev(), _p(ctx),
+                                          _rows2d(ctx, "ctx"), _p(lse), B, S, Sp, nh, span2, _stream()),
+         "fbl_disent_attn_fwd_qrows")
+
+
+def disent_attn_bwd_qrows_ws_bytes(R, Sp, nh):
+    return int(load().fbl_disent_attn_bwd_qrows_ws_bytes(R, Sp, nh))
+
+
+def disent_attn_bwd_qrows(q, rseg, rpos, k, v, pk, pq, relidx, mask, klen, dO, O, lse, scale, dQ, dK, dV, dPK, dPQ, rmin, rcnt, ws,
+                          B, S, Sp, nh, span2, p_drop=0.0, seed=0, row0=None):
+    """backward of disent_attn_fwd_qrows: dQ [R, .] compact, dK / dV for every key row of the layout, dPK / dPQ fp32
+    [nh, rcnt, 64] (table rows rmin ..); ws: uint8 workspace of disent_attn_bwd_qrows_ws_bytes(R, Sp, nh) bytes"""
+    R, ldp = _qrows_common(q, rseg, rpos, k, v, pk, pq, relidx, mask, klen, B, S)
+    for t, n in ((dO, "dO"), (O, "O"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")):
+        _req(t, torch.bfloat16, n)
+    assert (dPK is None) == (dPQ is None)  # both None: no table pass
+    for t, n in ((lse, "lse"),) + (((dPK, "dPK"), (dPQ, "dPQ")) if dPK is not None else ()):
+        _req(t, torch.float32, n)
+        assert t.is_contiguous(), n
+    assert dO.shape[0] == R and O.shape[0] == R and dQ.shape[0] == R and lse.numel() == nh * R
+    assert dPK is None or (dPK.numel() == nh * rcnt * 64 and dPQ.numel() == nh * rcnt * 64)
+    assert dK.shape[0] == k.shape[0] and dV.shape[0] == v.shape[0]
+    if R == 0:  # nothing selected: no launch, nothing written
+        return
+    assert ws.is_cuda and ws.is_contiguous()
+    _chk(load().fbl_disent_attn_bwd_qrows(_p(q), _rows2d(q, "q"), _p(rseg), _p(rpos), R, _p(k), _rows2d(k, "k"), _p(v),
+                                          _rows2d(v, "v"), _p(pk), _p(pq), ldp, _p(relidx), _p(mask), _p(klen),
+                                          _row0(row0, B, klen), _p(dO), _rows2d(dO, "dO"), _p(O), _rows2d(O, "O"), _p(lse),
+                                          float(scale), float(p_drop), int(seed), _seed_dev(), _p(dQ), _rows2d(dQ, "dQ"),
+                                          _p(dK), _rows2d(dK, "dK"), _p(dV), _rows2d(dV, "dV"), _p(dPK), _p(dPQ), int(rmin),
+                                          int(rcnt), _p(ws), ws.numel() * ws.element_size(), B, S, Sp, nh, span2, _stream()),
+         "fbl_disent_attn_bwd_qrows")
 
 
 def disent_attn_probs(q, k, pk, pq, relidx, mask, lse, scale, probs, B, S, nh):

@@ -33,6 +33,8 @@ def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, arg
     model.train()
     if getattr(args, "packed_rows", False) and hasattr(model, "packed_rows"):
         model.packed_rows = True  # opt-in: ragged batches without the padding rows behind each sample's last token
+    if getattr(args, "decoder_rows", False) and hasattr(model, "decoder_rows"):
+        model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, "Epoch: [{}]".format(epoch), epoch)
     log = LossLog(run, "mlm_loss", delayed=getattr(args, "delayed_loss_check", False), reducer=getattr(model, "_reducer", None))
     for i_batch, batch_dict in run:
@@ -48,6 +50,8 @@ def evaluate(model, tokenizer, data_loader, device, args):
     model.eval()
     if getattr(args, "packed_rows", False) and hasattr(model, "packed_rows"):
         model.packed_rows = True
+    if getattr(args, "decoder_rows", False) and hasattr(model, "decoder_rows"):
+        model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, "Val:")
     log = LossLog(run, "mlm_loss", stop_on_nonfinite=False, delayed=True)  # (nothing to protect: read one batch late)
     with frozen_weights(model):

@@ -63,6 +63,8 @@ def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, arg
     model.train()
     if getattr(args, "packed_rows", False) and hasattr(model, "packed_rows"):
         model.packed_rows = True  # ragged batches without the padding rows behind each sample's last token (implies the rows route)
+    if getattr(args, "decoder_rows", False) and hasattr(model, "decoder_rows"):
+        model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, "Epoch: [{}]".format(epoch), epoch)
     # several forwards feed one step: under data parallelism the gradient exchange waits for the last backward pass
     reducer = getattr(model.engine(), "reducer", None) if hasattr(model, "engine") else None
@@ -83,6 +85,8 @@ def evaluate(model, tokenizer, data_loader, device, dataset_name, args, split="t
         model.inference_graphs = True  # replay the per-batch forward as one hipGraph (fixed batch shapes pay off most)
     if getattr(args, "packed_rows", False) and hasattr(model, "packed_rows"):
         model.packed_rows = True  # ragged batches without the padding rows behind each sample's last token (takes precedence)
+    if getattr(args, "decoder_rows", False) and hasattr(model, "decoder_rows"):
+        model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, f"{split}:")
     res = {}
     with frozen_weights(model):  # nothing writes to the parameters during an evaluation: packed operands are reused

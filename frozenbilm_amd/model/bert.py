@@ -126,6 +126,7 @@ class BertForMaskedLM(nn.Module):
         self.inference_graphs = False
         self.training_graphs = False
         self.packed_rows = False
+        self.decoder_rows = False  # accepted, does nothing: this model has no enhanced mask decoder
         self._weights_frozen = 0
         self._reducer = None
         self.step_seed = 0

@@ -232,6 +232,8 @@ class DebertaV2ForMaskedLM(nn.Module):
         # that nothing on this path reads), training-mode dropout draws a different -- equally distributed -- mask stream, and
         # the launch graphs (shape-static) are not used while it is on.
         self.packed_rows = False
+        # opt-in: the two enhanced-mask-decoder passes, the head and their backward on the selected rows only (engine.py)
+        self.decoder_rows = False
         self._weights_frozen = 0  # nesting depth of weights_frozen(): inference forwards may reuse the packed operands
         self._reducer = None  # parallel.GradReducer attached to this model (survives engine rebuilds)
         self.step_seed = 0  # advanced every training forward; keys the counter-based dropout
@@ -469,7 +471,7 @@ class DebertaV2ForMaskedLM(nn.Module):
                 raise NotImplementedError("inputs_embeds is not on the FrozenBiLM hot path")
             raise ValueError("You have to specify either input_ids or inputs_embeds")
         eng = self.engine()
-        if (self.inference_graphs and not self.packed_rows and logit_rows is not None and labels is None and not output_hidden_states
+        if (self.inference_graphs and not self.packed_rows and not self.decoder_rows and logit_rows is not None and labels is None and not output_hidden_states
                 and not output_attentions and not self.training and not torch.is_grad_enabled()):
             logits = self._graph_forward(eng, input_ids, attention_mask, video, video_mask, mlm, logit_rows)
             if logits is not None:
@@ -480,7 +482,7 @@ class DebertaV2ForMaskedLM(nn.Module):
             from ..train_graph import restore_reducer_overlap
 
             restore_reducer_overlap(eng)  # graphs were on earlier in this run: give the reducer its overlap placement back
-        if (self.training_graphs and not self.packed_rows and self.training and labels is not None and not output_hidden_states
+        if (self.training_graphs and not self.packed_rows and not self.decoder_rows and self.training and labels is not None and not output_hidden_states
                 and not output_attentions
                 and logit_rows is None and not (self.n_ans and not mlm) and torch.is_grad_enabled()):
             from ..train_graph import graphed_forward

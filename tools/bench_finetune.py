@@ -10,11 +10,15 @@ Two workloads, each a full training step -- forward, the caller's loss on the [M
   mc       B = 8 questions x C = 4 candidates in ONE forward of 32 samples (mc.candidate_scores), ragged speech context up
            to S = 512, the 2-way answer head, balanced BCE on softmax[:, 0] (mc.py:64-92)
 
-Three legs per workload:
+Legs of these two workloads:
 
   full         the default route: full [B, S, n_ans] logits, head forward and backward on every token row
   rows         args.train_logit_rows: head forward and backward on the [MASK] rows only (logit_rows under autograd)
   rows_packed  args.packed_rows: the same on packed rows (model.packed_rows)
+  rows_decoder / rows_packed_decoder   the two above with args.decoder_rows: the enhanced mask decoder on the [MASK] rows only
+
+A third workload, `mlm`: B = 32, T = 10, ragged text U[32,256] with one sample of 256, labels on 15 % of the non-pad tokens,
+forward with `labels`, backward, clipped FusedAdam; legs `default` and `decoder_rows` (model.decoder_rows).
 
 The legs alternate inside one process (one model, one optimizer; every leg is a real update); per leg the median and the
 10th / 90th percentile over the timed iterations, and the share of token rows that exist on the packed layout.
@@ -38,7 +42,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=20, help="timed iterations per leg (at least 20 for the record)")
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--layers", type=int, default=0, help="encoder layers (0: the xlarge model's 24)")
-ap.add_argument("--only", choices=["videoqa", "mc"], default=None)
+ap.add_argument("--only", choices=["videoqa", "mc", "mlm"], default=None)
 a = ap.parse_args()
 dev = torch.device("cuda")
 T, FEAT, MASK = 10, 768, 128000
@@ -110,6 +114,7 @@ def workload(name):
     def step(**opt_in):
         args = types.SimpleNamespace(max_feats=T, use_video=True, **opt_in)
         m.packed_rows = bool(opt_in.get("packed_rows"))
+        m.decoder_rows = bool(opt_in.get("decoder_rows"))
         opt.zero_grad()
         logits = P_vqa.answer_logits(m, Tok, ids, args, **feed)
         if name == "videoqa":
@@ -119,7 +124,9 @@ def workload(name):
         loss.backward()
         opt.step(clip_max_norm=0.1)
 
-    legs = {"full": lambda: step(), "rows": lambda: step(train_logit_rows=True), "rows_packed": lambda: step(packed_rows=True)}
+    legs = {"full": lambda: step(), "rows": lambda: step(train_logit_rows=True), "rows_packed": lambda: step(packed_rows=True),
+            "rows_decoder": lambda: step(train_logit_rows=True, decoder_rows=True),
+            "rows_packed_decoder": lambda: step(packed_rows=True, decoder_rows=True)}
     res = {"shape": dict(samples=n, S=S, T=T, n_ans=n_ans, candidates=C, layers=cfg.num_hidden_layers, mask_rows=n),
            "rows": {"padded": n * S, "packed": rows_packed, "share": round(rows_packed / (n * S), 3)},
            "step_ms": alternate_stats(legs, a.steps, a.warmup)}
@@ -130,11 +137,48 @@ def workload(name):
     return res
 
 
+def workload_mlm():
+    cfg = DebertaV2Config()
+    if a.layers:
+        cfg.num_hidden_layers = a.layers
+    torch.manual_seed(0)
+    m = DebertaV2ForMaskedLM(cfg, max_feats=T, features_dim=FEAT, ds_factor_attn=8, ds_factor_ff=8, dropout=0.1)
+    m.to(dev).train()
+    opt = FusedAdam(m, lr=1e-5)
+    g = torch.Generator().manual_seed(4)
+    B, Lt = 32, 256
+    tlen = torch.randint(32, Lt + 1, (B,), generator=g)
+    tlen[-1] = Lt
+    valid = torch.arange(Lt)[None] < tlen[:, None]
+    ids = torch.randint(5, 127000, (B, Lt), generator=g) * valid
+    labels = torch.where(valid & (torch.rand(B, Lt, generator=g) < 0.15), ids, torch.full_like(ids, -100))
+    ids = torch.where(labels != -100, torch.full_like(ids, MASK), ids)
+    feed = dict(video=torch.randn(B, T, FEAT, generator=g).half().float().to(dev), video_mask=torch.ones(B, T, dtype=torch.long, device=dev),
+                input_ids=ids.to(dev), attention_mask=valid.long().to(dev), labels=labels.to(dev))
+
+    def step(on):
+        m.decoder_rows = on
+        opt.zero_grad()
+        m(**feed).loss.backward()
+        opt.step(clip_max_norm=0.1)
+
+    legs = {"default": lambda: step(False), "decoder_rows": lambda: step(True)}
+    res = {"shape": dict(samples=B, S=T + Lt, T=T, layers=cfg.num_hidden_layers, labelled_rows=int((labels != -100).sum()),
+                         rows=B * (T + Lt)),
+           "step_ms": alternate_stats(legs, a.steps, a.warmup)}
+    res["speedup_vs_default"] = round(res["step_ms"]["default"]["median"] / res["step_ms"]["decoder_rows"]["median"], 3)
+    del m, opt
+    torch.cuda.empty_cache()
+    return res
+
+
 out = {"device": torch.cuda.get_device_name(0),
-       "method": "device events around forward + loss + backward + clipped FusedAdam, train mode (dropout live); the three legs "
+       "method": "device events around forward + loss + backward + clipped FusedAdam, train mode (dropout live); the legs of a workload "
                  f"alternate inside one process; median, 10th and 90th percentile of {a.steps} timed iterations after {a.warmup} "
                  "warm-up iterations"}
 for w in ("videoqa", "mc"):
     if a.only in (None, w):
         out[w] = workload(w)
+if a.only in (None, "mlm"):
+    out["mlm"] = workload_mlm()
 print(json.dumps(out))
