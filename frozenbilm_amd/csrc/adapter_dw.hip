@@ -25,11 +25,6 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short tr16x4;
-__device__ __forceinline__ tr16x4 lds_tr16(const bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr16x4*)p);
-}
-
 constexpr int ADW_MAX_OUT = FBL_ADW_MAX_ADAPTERS;
 constexpr int ADW_MAX_SEG = FBL_ADW_MAX_SEGMENTS;
 

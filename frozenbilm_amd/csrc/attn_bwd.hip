@@ -1457,36 +1457,29 @@ extern "C" int fbl_disent_attn_bwd_ds(const void* q, const void* k, const void* 
                                       const int32_t* mask, const int32_t* klen, const int32_t* border, const float* lse, const float* Dv, float scale, float p_drop,
                                       uint64_t seed, const uint64_t* seed_dev, void* dV, int64_t lddv, void* dS, void* dST, int B, int S, int Sp,
                                       int nh, int span2, int lin_span, const int32_t* row0, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(S, Sp)) return FBL_ERR_SHAPE;
   if ((ldq % 8) || (ldo % 8) || (ldp % 8) || (lddv % 4)) return FBL_ERR_ALIGN;
   if (lin_span < 0 || 2 * lin_span > span2) return FBL_ERR_ARG;
   if (row0 && !klen) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
-  BwdAArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, ldq, (const bf16*)dO, ldo, (const bf16*)pk, (const bf16*)pq, ldp, relidx, mask, klen, border, lse, Dv, scale, p_drop, seed, (bf16*)dV, lddv,
-             (bf16*)dS, (bf16*)dST, B, S, Sp, nh, span2, lin_span, seed_dev, row0};
+  BwdAArgs a{};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ldq = ldq;
+  a.dO = (const bf16*)dO; a.ldo = ldo;
+  a.pk = (const bf16*)pk; a.pq = (const bf16*)pq; a.ldp = ldp;
+  a.relidx = relidx; a.mask = mask; a.klen = klen; a.border = border;
+  a.lse = lse; a.Dv = Dv;
+  a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
+  a.dV = (bf16*)dV; a.lddv = lddv; a.dS = (bf16*)dS; a.dST = (bf16*)dST;
+  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2; a.lin = lin_span;
+  a.row0 = row0;
   attn_debug_init();
-  const int smem_bytes = a_total(Sp);
-  static int attr_bytes = 0;
-  if (smem_bytes > attr_bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_ds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_ds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_ds_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_ds_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e != hipSuccess) return (int)e;
-    attr_bytes = smem_bytes;
-  }
   const dim3 grid((unsigned)(Sp / 64) * nh * B);
-  const bool devseed = seed_dev && p_drop > 0.f;
-  if (row0 && devseed)
-    hipLaunchKernelGGL((attn_bwd_ds_kernel<true, true>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);
-  else if (row0)
-    hipLaunchKernelGGL((attn_bwd_ds_kernel<false, true>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);
-  else if (devseed)
-    hipLaunchKernelGGL(attn_bwd_ds_kernel<true>, grid, dim3(256), smem_bytes, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(attn_bwd_ds_kernel<false>, grid, dim3(256), smem_bytes, (hipStream_t)stream, a);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return fbl_bool(seed_dev && p_drop > 0.f, [&](auto DEVSEED) {
+    return fbl_bool(row0 != nullptr, [&](auto PACKED) {
+      return fbl_launch<attn_bwd_ds_kernel<decltype(DEVSEED)::value, decltype(PACKED)::value>>(grid, dim3(256), a_total(Sp),
+                                                                                               stream, a);
+    });
+  });
 }
 
 extern "C" int fbl_disent_attn_bwd_dspk(const void* psave, const float* msave, const void* q, int64_t ldq, const void* v, int64_t ldv,
@@ -1494,92 +1487,72 @@ extern "C" int fbl_disent_attn_bwd_dspk(const void* psave, const float* msave, c
                                         const float* lse, const float* Dv, float scale, float p_drop, uint64_t seed,
                                         const uint64_t* seed_dev, void* dK, int64_t lddk, void* dV, int64_t lddv, void* dS, void* dST,
                                         int B, int S, int Sp, int nh, const int32_t* row0, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(S, Sp)) return FBL_ERR_SHAPE;
   if ((ldv % 8) || (ldo % 8) || (ldq % 8) || (lddv % 4) || (lddk % 4)) return FBL_ERR_ALIGN;
   if (!psave || !msave || !q || !v || !dO || !pqx || !lse || !Dv || !dK || !dV || !dS || !dST) return FBL_ERR_ARG;
   if (row0 && !klen) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
-  BwdPKArgs a{{(const bf16*)psave, msave, (const bf16*)v, ldv, (const bf16*)dO, ldo, klen, border, lse, Dv, scale, p_drop, seed,
-               seed_dev, (bf16*)dV, lddv, (bf16*)dS, (bf16*)dST, B, S, Sp, nh, row0},
-              (const bf16*)q, ldq, (const bf16*)pqx, (bf16*)dK, lddk};
+  BwdPKArgs a{};
+  a.p.psave = (const bf16*)psave; a.p.msave = msave;
+  a.p.v = (const bf16*)v; a.p.ldv = ldv; a.p.dO = (const bf16*)dO; a.p.ldo = ldo;
+  a.p.klen = klen; a.p.border = border; a.p.lse = lse; a.p.Dv = Dv;
+  a.p.scale = scale; a.p.p_drop = p_drop; a.p.seed = seed; a.p.seed_dev = seed_dev;
+  a.p.dV = (bf16*)dV; a.p.lddv = lddv; a.p.dS = (bf16*)dS; a.p.dST = (bf16*)dST;
+  a.p.B = B; a.p.S = S; a.p.Sp = Sp; a.p.nh = nh; a.p.row0 = row0;
+  a.q = (const bf16*)q; a.ldq = ldq; a.pqx = (const bf16*)pqx; a.dK = (bf16*)dK; a.lddk = lddk;
   attn_debug_init();
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dspk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, K_TOTAL);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dspk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, K_TOTAL);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const dim3 grid((unsigned)(Sp / 64) * nh * B);
-  if (row0)
-    hipLaunchKernelGGL(attn_bwd_dspk_kernel<true>, grid, dim3(256), K_TOTAL, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(attn_bwd_dspk_kernel<false>, grid, dim3(256), K_TOTAL, (hipStream_t)stream, a);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return fbl_bool(row0 != nullptr, [&](auto PACKED) {
+    return fbl_launch<attn_bwd_dspk_kernel<decltype(PACKED)::value>>(grid, dim3(256), K_TOTAL, stream, a);
+  });
 }
 
 extern "C" int fbl_disent_attn_bwd_dq(const void* dS, const void* k, int64_t ldk, const void* pkx, const int32_t* klen,
                                       const int32_t* border, void* dQ, int64_t lddq, int B, int S, int Sp, int nh,
                                       const int32_t* row0, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(S, Sp)) return FBL_ERR_SHAPE;
   if ((ldk % 8) || (lddq % 4)) return FBL_ERR_ALIGN;
   if (!dS || !k || !pkx || !dQ) return FBL_ERR_ARG;
   if (row0 && !klen) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
   BwdQArgs a{(const bf16*)dS, (const bf16*)k, ldk, (const bf16*)pkx, klen, border, (bf16*)dQ, lddq, B, S, Sp, nh, row0};
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, Q_TOTAL);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, Q_TOTAL);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const dim3 grid((unsigned)(Sp / 64) * nh * B);
-  if (row0)
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(256), Q_TOTAL, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(256), Q_TOTAL, (hipStream_t)stream, a);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return fbl_bool(row0 != nullptr, [&](auto PACKED) {
+    return fbl_launch<attn_bwd_dq_kernel<decltype(PACKED)::value>>(grid, dim3(256), Q_TOTAL, stream, a);
+  });
 }
 
 extern "C" int fbl_disent_attn_bwd_shear(const void* dST, const void* QT, int64_t y_sh, int64_t y_sb, int64_t y_sd,
                                          const void* PQT, const int16_t* relidx, const int32_t* klen, const int32_t* border,
                                          void* dK, int64_t lddk, int lin_span, int B, int S, int Sp, int nh, int span2,
                                          const int32_t* row0, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64 || span2 > 512 || span2 % 32) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(S, Sp) || span2 > 512 || span2 % 32) return FBL_ERR_SHAPE;
   if ((lddk % 4) || (y_sd % 8) || (y_sb % 8) || (y_sh % 8)) return FBL_ERR_ALIGN;
   if (B <= 0 || nh <= 0) return 0;
-  // index range reachable from 32 consecutive rows: <= S + 31 entries (idx has slope <= 1), +7 for the 8-alignment
-  int Wg = S + 31 + 7;
-  if (Wg > span2) Wg = span2;
-  Wg = (Wg + 31) / 32 * 32;
   if (row0 && !klen) return FBL_ERR_ARG;
-  ShearArgs a{(const bf16*)dST, (const bf16*)QT, y_sh, y_sb, y_sd, (const bf16*)PQT, relidx, klen, border, (bf16*)dK, lddk,
-              B, S, Sp, nh, span2, Wg, lin_span, row0};
+  ShearArgs a{};
+  a.X = (const bf16*)dST;
+  a.YT = (const bf16*)QT; a.y_sh = y_sh; a.y_sb = y_sb; a.y_sd = y_sd;
+  a.PT = (const bf16*)PQT;
+  a.relidx = relidx; a.klen = klen; a.border = border;
+  a.out = (bf16*)dK; a.ldout = lddk;
+  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2; a.lin = lin_span;
+  a.row0 = row0;
+  // index range reachable from 32 consecutive rows: <= S + 31 entries (idx has slope <= 1), +7 for the 8-alignment
+  a.Wg = S + 31 + 7;
+  if (a.Wg > span2) a.Wg = span2;
+  a.Wg = (a.Wg + 31) / 32 * 32;
   attn_debug_init();
-  const int smem_bytes = C_G + 32 * (Wg + 8) * 2;
-  static int attr_bytes = 0;
-  if (smem_bytes > attr_bytes) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)attn_bwd_shear_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e != hipSuccess) return (int)e;
-    attr_bytes = smem_bytes;
-  }
-  dim3 grid((unsigned)(Sp / 32) * nh * B);
-  if (row0)
-    hipLaunchKernelGGL(attn_bwd_shear_kernel<true>, grid, dim3(128), smem_bytes, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(attn_bwd_shear_kernel<false>, grid, dim3(128), smem_bytes, (hipStream_t)stream, a);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  const dim3 grid((unsigned)(Sp / 32) * nh * B);
+  return fbl_bool(row0 != nullptr, [&](auto PACKED) {
+    return fbl_launch<attn_bwd_shear_kernel<decltype(PACKED)::value>>(grid, dim3(128), C_G + 32 * (a.Wg + 8) * 2, stream, a);
+  });
 }
 
 extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* const* Y, int64_t ldy, const int16_t* dlo,
                                  const int16_t* dcnt, int dcnt_max, const int32_t* klen, const int32_t* row0, float* out, int E,
                                  int B, int S, int Sp, int nh, int rcnt, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64 || rcnt < 1 || rcnt > 1024) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(S, Sp) || rcnt < 1 || rcnt > 1024) return FBL_ERR_SHAPE;
   if (ldy % 8) return FBL_ERR_ALIGN;
   if (!X || !Y || !dlo || !dcnt || !out || dcnt_max < 1) return FBL_ERR_ARG;
   if (row0 && !klen) return FBL_ERR_ARG;
@@ -1589,28 +1562,8 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
   // three workgroups per CU (one staging buffer) where the rows are short enough for five chunks per thread, two otherwise
   static const int occ_sw = FBL_ENV_INT("FBL_POSGRAD_OCC", 3);
   const bool occ3 = Sp <= 320 && dcnt_max <= 3 && occ_sw >= 3;
-  const int smem_bytes = occ3 ? pg_buf(Sp) : pg_smem(Sp);
-  static int attr_bytes = 0;
-  if (pg_smem(Sp) > attr_bytes) {
-    const void* fns[6] = {(const void*)pos_grad_kernel<false, 3, 5, 3>, (const void*)pos_grad_kernel<true, 3, 5, 3>,
-                          (const void*)pos_grad_kernel<false, 3, 8, 2>, (const void*)pos_grad_kernel<true, 3, 8, 2>,
-                          (const void*)pos_grad_kernel<false, 8, 8, 2>, (const void*)pos_grad_kernel<true, 8, 8, 2>};
-    for (int i = 0; i < 6; ++i) {
-      hipError_t e1 = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, pg_smem(Sp));
-      if (e1 != hipSuccess) return (int)e1;
-    }
-    attr_bytes = pg_smem(Sp);
-  }
   // more than 8 deltas on a table row: the prefix-difference kernel (its own LDS budget)
   const bool wide = dcnt_max > 8;
-  static int attr_wide = 0;
-  if (wide && pgw_smem(Sp) > attr_wide) {
-    for (const void* fn : {(const void*)pos_grad_wide_kernel<false>, (const void*)pos_grad_wide_kernel<true>}) {
-      hipError_t e1 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, pgw_smem(Sp));
-      if (e1 != hipSuccess) return (int)e1;
-    }
-    attr_wide = pgw_smem(Sp);
-  }
   const int nsplit = (rcnt + PG_ROWS - 1) / PG_ROWS;
   for (int e0 = 0; e0 < E; e0 += PG_MAX_E) {
     PosGradArgs a{};
@@ -1622,24 +1575,15 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
     a.ldy = ldy; a.dlo = dlo; a.dcnt = dcnt; a.klen = klen; a.row0 = row0;
     a.out = out + (long)e0 * nh * rcnt * 64;
     a.E = ne; a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.rcnt = rcnt; a.cmax = dcnt_max;
-    const dim3 grid((unsigned)(((ne * nh + 7) / 8) * 8 * nsplit));
-#define FBL_PG_LAUNCH(NEG_, CM_, NXR_, OCC_) \
-  hipLaunchKernelGGL((pos_grad_kernel<NEG_, CM_, NXR_, OCC_>), grid, dim3(PG_THR), smem_bytes, (hipStream_t)stream, a)
-    if (wide) {
-      if (neg) hipLaunchKernelGGL(pos_grad_wide_kernel<true>, grid, dim3(PG_THR), pgw_smem(Sp), (hipStream_t)stream, a);
-      else hipLaunchKernelGGL(pos_grad_wide_kernel<false>, grid, dim3(PG_THR), pgw_smem(Sp), (hipStream_t)stream, a);
-    } else if (occ3) {
-      if (neg) FBL_PG_LAUNCH(true, 3, 5, 3);
-      else FBL_PG_LAUNCH(false, 3, 5, 3);
-    } else if (dcnt_max <= 3) {
-      if (neg) FBL_PG_LAUNCH(true, 3, 8, 2);
-      else FBL_PG_LAUNCH(false, 3, 8, 2);
-    } else {
-      if (neg) FBL_PG_LAUNCH(true, 8, 8, 2);
-      else FBL_PG_LAUNCH(false, 8, 8, 2);
-    }
-#undef FBL_PG_LAUNCH
-    FBL_CHECK_LAUNCH();
+    const dim3 grid((unsigned)(((ne * nh + 7) / 8) * 8 * nsplit)), block(PG_THR);
+    const int rc = fbl_bool(neg != 0, [&](auto NEG) {
+      constexpr bool N = decltype(NEG)::value;
+      if (wide) return fbl_launch<pos_grad_wide_kernel<N>>(grid, block, pgw_smem(Sp), stream, a);
+      if (occ3) return fbl_launch<pos_grad_kernel<N, 3, 5, 3>>(grid, block, pg_buf(Sp), stream, a);
+      if (dcnt_max <= 3) return fbl_launch<pos_grad_kernel<N, 3, 8, 2>>(grid, block, pg_smem(Sp), stream, a);
+      return fbl_launch<pos_grad_kernel<N, 8, 8, 2>>(grid, block, pg_smem(Sp), stream, a);
+    });
+    if (rc) return rc;
   }
   return 0;
 }
@@ -1653,9 +1597,16 @@ extern "C" int fbl_attn_bwd_prep(const void* q, int64_t ldq, const void* pq, con
   if (!Dv) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
   const int n_tr = (Sp / 64) * nh * B, n_tab = (span2 / 64) * nh, n_x = (2 * Sp / 64) * nh;
-  PrepArgs a{(const bf16*)q, ldq, (const bf16*)pq, (const bf16*)pk, ldp, (const bf16*)dO, (const bf16*)O, ldo, (bf16*)QT,
-             (bf16*)PQT, Dv, B, S, Sp, nh, span2, QT ? n_tr : 0, PQT ? n_tab : 0, row0, relidx, (bf16*)PQX, (bf16*)PKX,
-             PQX ? n_x : 0, PKX ? n_x : 0};
+  PrepArgs a{};
+  a.q = (const bf16*)q; a.ldq = ldq;
+  a.pq = (const bf16*)pq; a.pk = (const bf16*)pk; a.ldp = ldp;
+  a.dO = (const bf16*)dO; a.O = (const bf16*)O; a.ldo = ldo;
+  a.QT = (bf16*)QT; a.PQT = (bf16*)PQT; a.Dv = Dv;
+  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2;
+  a.n_qt = QT ? n_tr : 0; a.n_pqt = PQT ? n_tab : 0;
+  a.row0 = row0; a.relidx = relidx;
+  a.PQX = (bf16*)PQX; a.PKX = (bf16*)PKX;
+  a.n_pqx = PQX ? n_x : 0; a.n_pkx = PKX ? n_x : 0;
   const long n_dot = ((long)B * S * nh * 8 + 255) / 256;
   const long grid = (long)a.n_qt + a.n_pqt + a.n_pqx + a.n_pkx + n_dot;
   hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);

@@ -78,14 +78,6 @@ __device__ __forceinline__ WgCoord wg_coord(int nx, int nh, int B, const int32_t
   return c;
 }
 
-// ds_read_b64_tr_b16: the 16 lanes of a group each pass the address of 4 contiguous 16-bit elements -- together a
-// [4 rows][16 columns] block of a row-major LDS image (lane i: row i/4, columns (i%4)*4..+3) -- and lane i receives
-// column i of that block, i.e. 4 consecutive rows of one column (lane mapping probed in tools/probe/tr16_probe.hip).
-typedef __attribute__((ext_vector_type(4))) short tr16x4;
-__device__ __forceinline__ tr16x4 lds_tr16(const bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr16x4*)p);
-}
-
 constexpr float LOG2E = 1.4426950408889634f;
 
 // Buffer addressing for kernels that stream several tensors per loop iteration: a 128-bit descriptor of a WAVE-UNIFORM base in
@@ -165,5 +157,8 @@ __device__ __forceinline__ float attn_drop_keep(const DropKey& k, uint32_t x, ui
   const uint32_t f = pj ? (wsel >> 16) : (wsel & 0xffffu);
   return f >= k.thr16 ? k.inv_keep : 0.f;
 }
+
+// ---- host side: the tile grid every fused disentangled-attention entry point accepts (S positions padded to Sp, tiles of 64)
+static inline bool grid_shape_ok(int S, int Sp) { return S >= 1 && S <= 512 && Sp >= S && Sp % 64 == 0; }
 
 }  // namespace attn

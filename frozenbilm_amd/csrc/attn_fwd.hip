@@ -431,55 +431,39 @@ extern "C" int fbl_disent_attn_fwd(const void* q, int64_t ldq, const void* k, in
                                    const int32_t* border, float scale, float p_drop, uint64_t seed,
                                    const uint64_t* seed_dev, void* ctx, int64_t ldo, float* lse, int B, int S, int Sp, int nh, int span2,
                                    int lin_span, const int32_t* row0, void* psave, float* msave, void* stream) {
-  if (S < 1 || S > 512 || Sp < S || Sp % 64) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(S, Sp)) return FBL_ERR_SHAPE;
   if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldp % 8) || (ldo % 4)) return FBL_ERR_ALIGN;
   if (lin_span < 0 || 2 * lin_span > span2) return FBL_ERR_ARG;  // idx(0) +- (lin_span - 1 + 79) must stay inside the table
   if (row0 && !klen) return FBL_ERR_ARG;  // the packed layout is defined by the samples' lengths
   if ((psave != nullptr) != (msave != nullptr) || (psave && !lse)) return FBL_ERR_ARG;
   if (B <= 0 || nh <= 0) return 0;
-  AttnArgs a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)pk, (const bf16*)pq, ldq, ldk, ldp, ldv, relidx, mask, klen, border, scale, p_drop, seed, seed_dev, (bf16*)ctx, ldo, lse, B, S, Sp, nh, span2, lin_span, 0, row0,
-             (bf16*)psave, msave};
+  AttnArgs a{};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.pk = (const bf16*)pk; a.pq = (const bf16*)pq;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldp = ldp;
+  a.relidx = relidx; a.mask = mask; a.klen = klen; a.border = border;
+  a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
+  a.ctx = (bf16*)ctx; a.ldo = ldo; a.lse = lse;
+  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2; a.lin = lin_span;
+  a.row0 = row0; a.psave = (bf16*)psave; a.msave = msave;
   static const int dbg = FBL_ENV_INT("FBL_ATTN_DBG", 0);
   a.dbg = dbg;
   attn_debug_init();
-  const int smem_bytes = sm_total(Sp);
-  // three workgroups per CU (<= 168 VGPRs) AND a register prefetch of the next key tile, in flight during the gather / softmax /
+  const dim3 grid((unsigned)((S + 63) / 64) * nh * B);
+  // One launch, of the instantiation the arguments select: packed rows (row0) x saved probabilities (psave).  All of them run
+  // three workgroups per CU (<= 168 VGPRs) with a register prefetch of the next key tile in flight during the gather / softmax /
   // P.V phase: 98 -> 96.6 us alone (an earlier prefetching version lost, 97.2 vs 88.6 us, because its registers spilled; this
   // one has no spills).  The kernels without the prefetch exist in the measurement build only (FBL_ATTN_PF=0).
-  static int attr_bytes = 0;
-  if (smem_bytes > attr_bytes) {
-    const void* fns[] = {(const void*)attn_fwd_kernel<3, true>, (const void*)attn_fwd_kernel<3, true, true>,
-                         (const void*)attn_fwd_kernel<3, true, false, true>, (const void*)attn_fwd_kernel<3, true, true, true>,
-#ifdef FBL_DEBUG_SWITCHES
-                         (const void*)attn_fwd_kernel<3, false>, (const void*)attn_fwd_kernel<3, false, true>,
-                         (const void*)attn_fwd_kernel<3, false, false, true>, (const void*)attn_fwd_kernel<3, false, true, true>,
-#endif
-    };
-    for (const void* fn : fns) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_bytes = smem_bytes;
-  }
-  dim3 grid((unsigned)((S + 63) / 64) * nh * B);
-#define FBL_FWD_LAUNCH(PF_)                                                                                             \
-  do {                                                                                                                  \
-    if (row0 && psave)                                                                                                  \
-      hipLaunchKernelGGL((attn_fwd_kernel<3, PF_, true, true>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);   \
-    else if (row0)                                                                                                      \
-      hipLaunchKernelGGL((attn_fwd_kernel<3, PF_, true>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);         \
-    else if (psave)                                                                                                     \
-      hipLaunchKernelGGL((attn_fwd_kernel<3, PF_, false, true>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);  \
-    else                                                                                                                \
-      hipLaunchKernelGGL((attn_fwd_kernel<3, PF_>), grid, dim3(256), smem_bytes, (hipStream_t)stream, a);               \
-  } while (0)
+  auto launch = [&](auto PF) {
+    return fbl_bool(row0 != nullptr, [&](auto PACKED) {
+      return fbl_bool(psave != nullptr, [&](auto SAVEP) {
+        return fbl_launch<attn_fwd_kernel<3, decltype(PF)::value, decltype(PACKED)::value, decltype(SAVEP)::value>>(
+            grid, dim3(256), sm_total(Sp), stream, a);
+      });
+    });
+  };
 #ifdef FBL_DEBUG_SWITCHES
   static const int pf = FBL_ENV_INT("FBL_ATTN_PF", 1);  // 0: no register prefetch of the next key tile
-  if (!pf) FBL_FWD_LAUNCH(false);
-  else
+  if (!pf) return launch(std::false_type{});
 #endif
-    FBL_FWD_LAUNCH(true);
-#undef FBL_FWD_LAUNCH
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return launch(std::true_type{});
 }

@@ -456,7 +456,7 @@ int qr_check(const QrArgs& a) {
   if (!a.rseg || !a.rpos || !a.klen) return FBL_ERR_ARG;
   if (a.R < 0) return FBL_ERR_ARG;
   if (!(a.p_drop >= 0.f && a.p_drop < 1.f)) return FBL_ERR_ARG;
-  if (a.S < 1 || a.S > 512 || a.Sp < a.S || a.Sp % 64 || a.span2 < 1 || a.span2 > QR_MAX_SPAN2) return FBL_ERR_SHAPE;
+  if (!grid_shape_ok(a.S, a.Sp) || a.span2 < 1 || a.span2 > QR_MAX_SPAN2) return FBL_ERR_SHAPE;
   if ((a.ldq % 8) || (a.ldk % 8) || (a.ldv % 8) || (a.ldp % 8) || (a.ldo % 8)) return FBL_ERR_ALIGN;
   if (mis16(a.q) || mis16(a.k) || mis16(a.v) || mis16(a.pk) || mis16(a.pq) || mis16(a.ctx)) return FBL_ERR_ALIGN;
   if (!a.q || !a.k || !a.v || !a.pk || !a.pq || !a.relidx || !a.mask || !a.ctx || !a.lse) return FBL_ERR_ARG;
@@ -465,15 +465,9 @@ int qr_check(const QrArgs& a) {
 
 template <bool BWD>
 int qr_launch_rows(const QrArgs& a, hipStream_t st) {
-  const int smem_bytes = qr_smem(a.Sp, a.span2, BWD);
-  // (set on every call: the attribute is per device and the call is cheap next to a launch)
-  hipError_t e = hipFuncSetAttribute((const void*)qrows_kernel<BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-  if (e != hipSuccess) return (int)e;
   // an upper bound of the number of 16-row groups that needs no look at rseg: sum_b ceil(n_b / 16) <= R / 16 + B
   dim3 grid((unsigned)(a.R / 16 + a.B), (unsigned)a.nh);
-  hipLaunchKernelGGL(qrows_kernel<BWD>, grid, dim3(64), smem_bytes, st, a);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return fbl_launch<qrows_kernel<BWD>>(grid, dim3(64), qr_smem(a.Sp, a.span2, BWD), st, a);
 }
 
 }  // namespace

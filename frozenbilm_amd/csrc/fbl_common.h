@@ -1,7 +1,8 @@
-// Device-side helpers shared by the gfx950 kernels of libfbl.  CDNA4 only: wave = 64 lanes.
+// Device-side helpers shared by the gfx950 kernels of libfbl (CDNA4 only: wave = 64 lanes), and the host-side launch helper.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -27,8 +28,45 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
     if (e__ != hipSuccess) return (int)e__;                    \
   } while (0)
 
+// ---- host side: the one place where a kernel with dynamic LDS is launched.
+// fbl_launch<kernel>(grid, block, lds_bytes, stream, args...) raises the kernel's dynamic-LDS limit when lds_bytes exceeds
+// what this (instantiation, current device) pair has been given so far, launches, and returns hipGetLastError() as the
+// library's int.  The opt-in happens inside the launch, so the instantiations that get the attribute are by construction
+// the ones that are launched.  The high-water marks are per device (the attribute is); two threads racing on one only set
+// the attribute twice.
+constexpr int FBL_MAX_DEVICES = 64;  // an arbitrary bound, far above any node's: an index beyond it is served without the cache
+template <auto Kernel, typename... Args>
+static inline int fbl_launch(dim3 grid, dim3 block, int lds_bytes, void* stream, const Args&... args) {
+  static int lds_given[FBL_MAX_DEVICES] = {};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return (int)e;
+  const bool cached = dev >= 0 && dev < FBL_MAX_DEVICES;
+  if (!cached || lds_bytes > lds_given[dev]) {
+    e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    if (cached) lds_given[dev] = lds_bytes;
+  }
+  Kernel<<<grid, block, lds_bytes, (hipStream_t)stream>>>(args...);
+  return (int)hipGetLastError();
+}
+// bool -> template flag, each combination written once (nestable):
+//   fbl_bool(row0 != nullptr, [&](auto PACKED) { return fbl_launch<kern<decltype(PACKED)::value>>(...); })
+template <typename F>
+static inline int fbl_bool(bool cond, F&& f) {
+  return cond ? f(std::true_type{}) : f(std::false_type{});
+}
+
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }  // RNE (v_cvt_pk_bf16_f32 on gfx950)
+
+// ds_read_b64_tr_b16: the 16 lanes of a group each pass the address of 4 contiguous 16-bit elements -- together a
+// [4 rows][16 columns] block of a row-major LDS image (lane i: row i/4, columns (i%4)*4..+3) -- and lane i receives
+// column i of that block, i.e. 4 consecutive rows of one column (lane mapping probed in tools/probe/tr16_probe.hip).
+typedef __attribute__((ext_vector_type(4))) short tr16x4;
+__device__ __forceinline__ tr16x4 lds_tr16(const bf16* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr16x4*)p);
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -175,10 +175,6 @@ struct GemmTnArgs {
   float* ws; int Nw;  // partials [splitk][M][Nw]
   int splitk, tiles_m, tiles_n;
 };
-typedef __attribute__((ext_vector_type(4))) short tr16x4;
-__device__ __forceinline__ tr16x4 lds_tr16(const bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tr16x4*)p);
-}
 constexpr int TN_LD = 136;  // bf16 row stride of the staged [64 k][128 cols] tiles (272 B: 16B-aligned rows)
 
 __global__ __launch_bounds__(256, 2) void gemm_bf16_tn_kernel(GemmTnArgs g) {
@@ -504,16 +500,7 @@ template <int NW, int ACT, int AUX, bool SPLITK, bool RING, int MI>
 static int launch_nt(const GemmArgs& g, dim3 grid, hipStream_t stream) {
   constexpr int smem_bytes = RING ? 3 * (32 * MI * BK * 2 + TileCfg<NW>::TILE_BYTES) : TileCfg<NW>::SMEM_BYTES;
   static_assert(smem_bytes >= NW * 64 * 68 * 4, "the LDS must cover the epilogue staging");
-  static bool attr_set = false;
-  auto kfn = gemm_bf16_nt_kernel<NW, ACT, AUX, SPLITK, RING, MI>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, smem_bytes);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kfn, grid, dim3(NW * 64), smem_bytes, stream, g);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return fbl_launch<gemm_bf16_nt_kernel<NW, ACT, AUX, SPLITK, RING, MI>>(grid, dim3(NW * 64), smem_bytes, stream, g);
 }
 
 template <int ACT, int AUX>

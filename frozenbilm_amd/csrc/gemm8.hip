@@ -268,54 +268,36 @@ __global__ __launch_bounds__(512, 2) void gemm8_kernel(GemmArgs g) {
                                                             R128 ? 32 : (short_rows ? 48 : 64));
 }
 
+template <int ACT, int AUX, int RT, int VAR>
+int launch_g8(const GemmArgs& g, dim3 grid, hipStream_t stream) {
+  return fbl_launch<gemm8_kernel<ACT, AUX, VAR, RT>>(grid, dim3(512), SMEM8_BYTES, stream, g);
+}
+
 template <int ACT, int AUX, int RT>
 int launch_variant(const GemmArgs& g, dim3 grid, hipStream_t stream) {
   static const int var = FBL_ENV_INT("FBL_GEMM8_VAR", 3);
-#define FBL_G8_LAUNCH(VAR_)                                                                                     \
-  do {                                                                                                          \
-    static bool attr_set = false;                                                                               \
-    auto kfn = gemm8_kernel<ACT, AUX, VAR_, RT>;                                                                \
-    if (!attr_set) {                                                                                            \
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM8_BYTES); \
-      if (e != hipSuccess) return (int)e;                                                                       \
-      attr_set = true;                                                                                          \
-    }                                                                                                           \
-    hipLaunchKernelGGL(kfn, grid, dim3(512), SMEM8_BYTES, stream, g);                                           \
-  } while (0)
 #ifdef FBL_DEBUG_SWITCHES
   if constexpr ((ACT == FBL_ACT_NONE || ACT == FBL_ACT_GELU_GRAD) && AUX == FBL_AUX_NONE && RT == 0) {  // experiment variants
-    if (var == 0) FBL_G8_LAUNCH(0);
-    else if (var == 1) FBL_G8_LAUNCH(1);
-    else if (var == 2) FBL_G8_LAUNCH(2);
-    else if (var == 7) FBL_G8_LAUNCH(7);
-    else if (var == 11) FBL_G8_LAUNCH(11);  // no global stores
-    else if (var == 19) FBL_G8_LAUNCH(19);  // stores alias 256 rows
-    else FBL_G8_LAUNCH(3);
-  } else {
-    FBL_G8_LAUNCH(3);
+    switch (var) {
+      case 0: return launch_g8<ACT, AUX, RT, 0>(g, grid, stream);
+      case 1: return launch_g8<ACT, AUX, RT, 1>(g, grid, stream);
+      case 2: return launch_g8<ACT, AUX, RT, 2>(g, grid, stream);
+      case 7: return launch_g8<ACT, AUX, RT, 7>(g, grid, stream);
+      case 11: return launch_g8<ACT, AUX, RT, 11>(g, grid, stream);  // no global stores
+      case 19: return launch_g8<ACT, AUX, RT, 19>(g, grid, stream);  // stores alias 256 rows
+      default: break;
+    }
   }
-#else
-  FBL_G8_LAUNCH(3);
 #endif
-#undef FBL_G8_LAUNCH
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return launch_g8<ACT, AUX, RT, 3>(g, grid, stream);
 }
 
 }  // namespace
 
 // split-K launch of the plain 256-row configuration: grid (tiles, slices)
 int launch_gemm8_splitk(const GemmArgs& g, hipStream_t stream) {
-  static bool attr_set = false;
-  auto kfn = gemm8_kernel<FBL_ACT_NONE, FBL_AUX_NONE, 3, 0, true>;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM8_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(512), SMEM8_BYTES, stream, g);
-  FBL_CHECK_LAUNCH();
-  return 0;
+  return fbl_launch<gemm8_kernel<FBL_ACT_NONE, FBL_AUX_NONE, 3, 0, true>>(dim3(g.tiles_m * g.tiles_n, g.splitk), dim3(512),
+                                                                          SMEM8_BYTES, stream, g);
 }
 
 bool gemm8_eligible(const GemmArgs& g) {

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional
 
 import torch
@@ -19,85 +20,49 @@ ACT_NONE, ACT_GELU, ACT_RELU, ACT_GELU_GRAD = 0, 1, 2, 3
 AUX_NONE, AUX_ADD_F32, AUX_ADD_BF16, AUX_MUL_DGELU_BF16, AUX_MUL_POS_BF16, AUX_MUL_BF16 = 0, 1, 2, 3, 4, 5
 ABI_VERSION = 9  # fbl_abi_version() of the library this binding was written against (argument lists change with it)
 
-_vp, _i, _l, _f, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
+# C type of a declaration -> ctypes; any pointer is passed as c_void_p (device pointers, host tables and the stream alike)
+_CTYPES = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "uint64_t": C.c_uint64}
+_DECL = re.compile(r"(?:^|[;{}])\s*([\w\s*]+?)\s*\b(fbl_\w+)\s*\(([^;()]*)\)\s*(?=;)")
 
-# name -> (restype, argtypes); must mirror include/fbl.h (tests/test_abi.py checks both directions)
-SIGNATURES = {
-    "fbl_abi_version": (_i, []),
-    "fbl_gemm_bf16_nt": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _l, _vp, _vp, _vp, _l, _i, _l, _l,
-                              _l, _l, _l, _i, _vp, _l, _vp, _vp]),
-    "fbl_adapter_down_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _f, _u64, _vp, _vp, _l, _vp]),
-    "fbl_dense_adapter_down_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp, _vp, _l, _f, _u64, _vp, _vp, _l, _vp, _vp]),
-    "fbl_adapter_up_resid_fwd": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _l, _f, _u64, _vp, _vp, _l, _vp, _vp, _vp, _vp,
-                                      _vp, _l, _vp]),
-    "fbl_gemm_bf16_tn_acc": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp, _l, _i, _vp, _l, _vp]),
-    "fbl_adapter_bwd_dw": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "fbl_embed_gather": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_gemm_plan": (_i, [_i, _i, _i, _i, _i]),
-    "fbl_gemm_plan_launches": (_i, [_i, _i, _i, _i, _l, _l, _l, _l, _i, _i, _i, _i, _i, _i, _l, _i, _vp]),
-    "fbl_ln_fwd": (_i, [_vp, _l, _f, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _i,
-                        _vp]),
-    "fbl_ln_materialize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
-    "fbl_ln_bwd_ws_floats": (_l, [_i]),
-    "fbl_ln_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _l, _vp]),
-    "fbl_im2col3": (_i, [_vp, _vp, _i, _i, _i, _vp]),
-    "fbl_col2im3": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "fbl_dropout_gelu_fwd": (_i, [_vp, _f, _u64, _vp, _vp, _l, _vp]),
-    "fbl_dropout_gelu_bwd": (_i, [_vp, _vp, _f, _u64, _vp, _vp, _vp, _l, _vp]),
-    "fbl_video_stage_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "fbl_mask_tokens": (_i, [_vp, _vp, _l, _vp, _i, _f, _l, _l, _u64, _vp]),
-    "fbl_transpose_to_bf16": (_i, [_vp, _i, _l, _i, _i, _vp, _l, _vp]),
-    "fbl_transpose_batched_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "fbl_colsum_ws_floats": (_l, [_i]),
-    "fbl_colsum": (_i, [_vp, _i, _l, _i, _i, _vp, _vp, _vp]),
-    "fbl_head_transpose": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _l, _l, _l, _vp]),
-    "fbl_disent_attn_fwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l,
-                                 _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "fbl_disent_attn_probs": (_i, [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
-    "fbl_attn_rowdot": (_i, [_vp, _vp, _l, _vp, _i, _i, _i, _vp]),
-    "fbl_attn_bwd_prep": (_i, [_vp, _l, _vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_disent_attn_bwd_dq": (_i, [_vp, _vp, _l, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_disent_attn_bwd_dspk": (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l,
-                                      _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_disent_attn_bwd_ds": (_i, [_vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _f, _f, _u64, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_disent_attn_bwd_shear": (_i, [_vp, _vp, _l, _l, _l, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "fbl_attn_pos_grad": (_i, [_i, _vp, _vp, _l, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "fbl_ce_fwd": (_i, [_vp, _l, _vp, _i, _i, _vp, _vp, _vp]),
-    "fbl_ce_bwd_rows": (_i, [_vp, _l, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp]),
-    "fbl_gather_rows_bf16": (_i, [_vp, _l, _vp, _i, _i, _vp, _vp]),
-    "fbl_scatter_rows_f32": (_i, [_vp, _vp, _i, _i, _vp, _l, _vp]),
-    "fbl_sumsq_ws_floats": (_l, []),
-    "fbl_sumsq": (_i, [_vp, _l, _vp, _vp, _vp]),
-    "fbl_adam_flat": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp, _f, _f, _vp]),
-    "fbl_cast_f32_to_bf16": (_i, [_vp, _vp, _l, _vp]),
-    "fbl_dropout_f32": (_i, [_vp, _f, _u64, _vp, _vp, _vp, _l, _vp]),
-    "fbl_dropout_bf16": (_i, [_vp, _f, _u64, _vp, _l, _vp]),
-    "fbl_dropout_sum_f32": (_i, [_vp, _l, _l, _i, _vp, _f, _vp, _vp, _vp]),
-    "fbl_zero": (_i, [_vp, _l, _vp]),
-    "fbl_heads_to_rows_bf16": (_i, [_vp, _vp, _i, _i, _i, _l, _vp]),
-}
 
-# the BERT variant's fused attention (include/fbl_mha.h): same library, a table of its own so that SIGNATURES keeps mirroring
-# include/fbl.h exactly
-MHA_SIGNATURES = {
-    "fbl_mha_fwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _i, _i, _i, _vp]),
-    "fbl_mha_bwd": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l, _vp, _l,
-                         _i, _i, _i, _vp]),
-    "fbl_mha_fwd_rows": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _i, _i, _i, _vp]),
-    "fbl_mha_bwd_rows": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp, _vp, _l,
-                              _vp, _l, _vp, _l, _i, _i, _i, _vp]),
-}
+def _ctype(text: str, decl: str):
+    if "*" in text:
+        return C.c_void_p
+    words = [w for w in text.split() if w != "const"]  # "int64_t ldq" / "int" (a return type or an unnamed parameter)
+    if not 1 <= len(words) <= 2 or words[0] not in _CTYPES or not words[-1].isidentifier():  # (an array `int x[4]` is no int)
+        raise ValueError(f"{decl}: no ctypes mapping for '{text.strip()}'")
+    return _CTYPES[words[0]]
 
-# the enhanced mask decoder's attention on selected query rows (include/fbl_qrows.h): a table of its own for the same reason
-QROWS_SIGNATURES = {
-    "fbl_disent_attn_fwd_qrows": (_i, [_vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _f, _f, _u64, _vp,
-                                       _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
-    "fbl_disent_attn_bwd_qrows_ws_bytes": (_l, [_i, _i, _i]),
-    "fbl_disent_attn_bwd_qrows": (_i, [_vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l,
-                                       _vp, _f, _f, _u64, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp, _l, _i, _i, _i,
-                                       _i, _i, _vp]),
-}
+
+def parse_signatures(src: str) -> dict:
+    """name -> (restype, argtypes) of every `fbl_*` function declared in the C source text `src`"""
+    src = re.sub(r"/\*.*?\*/|//[^\n]*", "", src, flags=re.S)
+    src = re.sub(r"^[ \t]*#.*$", "", src, flags=re.M)
+    out = {}
+    for ret, name, params in _DECL.findall(src):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype(ret, name), [_ctype(p, name) for p in params])
+    # _DECL knows plain parameter lists only: anything else that looks like an fbl_* function (a function-pointer parameter,
+    # a macro call among the parameters) is an error too, not a declaration quietly left out of the table
+    unparsed = set(re.findall(r"\b(fbl_\w+)\s*\(", src)) - set(out)
+    if unparsed:
+        raise ValueError(f"{', '.join(sorted(unparsed))}: declaration not understood")
+    return out
+
+
+def _header_signatures(header: str) -> dict:
+    p = os.path.join(os.path.dirname(HERE), "include", header)
+    if not os.path.exists(p):
+        raise RuntimeError(f"{p} not found: the binding of libfbl.so takes its argument types from the C headers")
+    with open(p) as f:
+        return parse_signatures(f.read())
+
+
+# name -> (restype, argtypes), one table per header, derived from the declarations the library itself is compiled against
+# (tests/test_abi.py, test_mha_abi.py and test_qrows_abi.py cross-check them with parsers of their own)
+SIGNATURES = _header_signatures("fbl.h")
+MHA_SIGNATURES = _header_signatures("fbl_mha.h")      # the BERT variant's fused attention
+QROWS_SIGNATURES = _header_signatures("fbl_qrows.h")  # the enhanced mask decoder's attention on selected query rows
 
 _LIB = None
 

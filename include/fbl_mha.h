@@ -1,7 +1,7 @@
 /* libfbl -- fused multi-head attention of the BERT variant (MI355X, gfx950).  Same library, same conventions as fbl.h:
  * extern "C", plain device pointers + sizes, `stream` a hipStream_t passed as void*, every function only enqueues work
  * (graph-capturable, no allocation / copy / sync inside), returns 0, a positive hipError_t or a negative FBL_ERR_* code.
- * Dropout seeds as in fbl.h ("Dropout seeds").  Bound from Python by frozenbilm_amd/lib.py MHA_SIGNATURES.
+ * Dropout seeds as in fbl.h ("Dropout seeds").  Bound from Python by frozenbilm_amd/lib.py MHA_SIGNATURES, derived from this header.
  */
 #ifndef FBL_MHA_H
 #define FBL_MHA_H

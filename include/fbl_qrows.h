@@ -2,7 +2,7 @@
  * when only a few token rows reach the prediction head.  Same library, same conventions as fbl.h: extern "C", plain device
  * pointers + sizes, `stream` a hipStream_t passed as void*, every function only enqueues work (no allocation / copy / sync
  * inside), returns 0, a positive hipError_t or a negative FBL_ERR_* code.  Dropout seeds as in fbl.h ("Dropout seeds").
- * Bound from Python by frozenbilm_amd/lib.py QROWS_SIGNATURES.
+ * Bound from Python by frozenbilm_amd/lib.py QROWS_SIGNATURES, derived from this header.
  */
 #ifndef FBL_QROWS_H
 #define FBL_QROWS_H
