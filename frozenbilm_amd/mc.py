@@ -65,6 +65,14 @@ def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, arg
         model.packed_rows = True  # ragged batches without the padding rows behind each sample's last token (implies the rows route)
     if getattr(args, "decoder_rows", False) and hasattr(model, "decoder_rows"):
         model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
+    if getattr(args, "finetune_graphs", False) and hasattr(model, "finetune_graphs"):
+        if getattr(args, "mc_sequential", False):  # one forward per candidate, all alive until the step's backward: a captured
+            import warnings                        # step owns ONE set of activations, so this loop stays on the eager rows route
+
+            warnings.warn("args.finetune_graphs is not used with args.mc_sequential (several forwards alive per step); "
+                          "running the steps eagerly")
+        else:
+            model.finetune_graphs = True  # replay the step's forward and backward as two hipGraphs per length bucket
     run = EpochRunner(data_loader, args, "Epoch: [{}]".format(epoch), epoch)
     # several forwards feed one step: under data parallelism the gradient exchange waits for the last backward pass
     reducer = getattr(model.engine(), "reducer", None) if hasattr(model, "engine") else None

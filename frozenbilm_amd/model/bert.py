@@ -125,6 +125,7 @@ class BertForMaskedLM(nn.Module):
         # packed_rows is honoured (bert_engine.bert_packing)
         self.inference_graphs = False
         self.training_graphs = False
+        self.finetune_graphs = False
         self.packed_rows = False
         self.decoder_rows = False  # accepted, does nothing: this model has no enhanced mask decoder
         self._weights_frozen = 0

@@ -226,6 +226,9 @@ class DebertaV2ForMaskedLM(nn.Module):
         self.engine_options = {}  # read once when the engine is built (engine.Engine.__init__ lists the keys; defaults = shipped)
         self.inference_graphs = False  # opt-in: replay the `logit_rows` inference forward as one hipGraph (_graph_forward)
         self.training_graphs = False  # opt-in: the MLM training step as two replayed hipGraphs (train_graph.py)
+        # opt-in: the fine-tuning step (`logit_rows` under autograd, no labels) as two replayed hipGraphs, the text padded to a
+        # length bucket of GRAPH_L_BUCKET; not used while packed_rows / decoder_rows is on (train_graph.finetune_forward)
+        self.finetune_graphs = False
         # opt-in: ragged batches run without the padding rows behind each sample's last used position (engine.Packing) whenever
         # the call's outputs live on selected rows (labels / logit_rows given).  Rows that exist get the same values as on the
         # padded grid; `logits` / `hidden_states` read as zero at the dropped positions (the reference computes values there
@@ -322,6 +325,7 @@ class DebertaV2ForMaskedLM(nn.Module):
         self._engine = None
         self.__dict__.pop("_graph_cache", None)  # captured graphs hold the old engine's buffers
         self.__dict__.pop("_train_graphs", None)
+        self.__dict__.pop("_finetune_graph_cache", None)
 
     def _load_from_state_dict(self, *a, **k):
         self.invalidate()
@@ -381,14 +385,14 @@ class DebertaV2ForMaskedLM(nn.Module):
         eng.prepare_inference()
         B, Lt = input_ids.shape
         T = video.shape[1] if (video is not None and eng.F) else 0
-        Lp = min(-(-Lt // self.GRAPH_L_BUCKET) * self.GRAPH_L_BUCKET, self.config.max_position_embeddings - T)
-        if Lp < Lt:
+        from ..train_graph import bucket_length, remap_rows
+
+        Lp = bucket_length(Lt, T, self.config.max_position_embeddings, self.GRAPH_L_BUCKET)
+        if Lp is None:
             return None
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        rows = logit_rows.to(eng.dev).long().view(-1)
-        S_old, S_new = T + Lt, T + Lp
-        rows = (rows // S_old) * S_new + rows % S_old
+        rows = remap_rows(logit_rows.to(eng.dev).long().view(-1), T + Lt, T + Lp)
         key = (id(eng), B, Lp, T, video_mask is not None, rows.numel(), bool(mlm))
         cache = self.__dict__.setdefault("_graph_cache", {})
         feed = dict(input_ids=F_.pad(input_ids, (0, Lp - Lt), value=self.config.pad_token_id),
@@ -477,8 +481,9 @@ class DebertaV2ForMaskedLM(nn.Module):
             if logits is not None:
                 out = MaskedLMOutput(loss=None, logits=logits, hidden_states=None, attentions=None)
                 return out if return_dict is not False else (logits,)
-        if (not self.training_graphs and eng.reducer is not None and "_overlap_before_graphs" in eng.reducer.__dict__
-                and not self.__dict__.get("_train_graphs_auto_off")):
+        if (not self.training_graphs and not self.finetune_graphs and eng.reducer is not None
+                and "_overlap_before_graphs" in eng.reducer.__dict__ and not self.__dict__.get("_train_graphs_auto_off")
+                and not self.__dict__.get("_finetune_graphs_auto_off")):
             from ..train_graph import restore_reducer_overlap
 
             restore_reducer_overlap(eng)  # graphs were on earlier in this run: give the reducer its overlap placement back
@@ -497,6 +502,17 @@ class DebertaV2ForMaskedLM(nn.Module):
                 out.__dict__["_run"] = run
                 out.__dict__["_fill"] = lambda: eng.fill_logits(run)
                 return out if return_dict is not False else (out["loss"], out["logits"])
+        if (self.finetune_graphs and not self.packed_rows and not self.decoder_rows and self.training and logit_rows is not None
+                and labels is None and not output_hidden_states and not output_attentions and torch.is_grad_enabled()
+                and logit_rows.numel() > 0):
+            from ..train_graph import finetune_forward
+
+            got = finetune_forward(self, eng, input_ids, attention_mask, video, video_mask, mlm, logit_rows)
+            if got is not None:
+                logits, run = got
+                out = MaskedLMOutput(loss=None, logits=logits, hidden_states=None, attentions=None)
+                out.__dict__["_run"] = run
+                return out if return_dict is not False else (logits,)
         # output_attentions=True (model/deberta.py:1414-1427, :544-560): the fused attention kernel never materialises its
         # probabilities; on request a plain kernel rebuilds them per encoder layer from the stored log-sum-exp (eval mode)
         res = eng.run(input_ids, attention_mask, video, video_mask, labels, mlm, output_hidden_states, logit_rows=logit_rows,

@@ -32,10 +32,12 @@ def mask_rows(encoded_ids, tokenizer, args, device):
 def answer_logits(model, tokenizer, encoded_ids, args, **feed):
     """Logits of the [MASK] rows, [n_mask, n_ans].  Without gradients the HIP model runs its prediction head on those rows
     only (``logit_rows``).  A training pass does the same -- head forward and backward on the [MASK] rows -- when the caller
-    opts in with ``args.train_logit_rows``, ``args.packed_rows`` or ``args.decoder_rows`` (both need the rows); any other model, and a training
-    pass without the opt-in, takes the reference's route: full logits, then the row selection of videoqa.py:164-168."""
+    opts in with ``args.train_logit_rows``, ``args.packed_rows``, ``args.decoder_rows`` or ``args.finetune_graphs`` (the last
+    three need the rows); any other model, and a training pass without the opt-in, takes the reference's route: full logits, then
+    the row selection of videoqa.py:164-168."""
     rows_route = (not torch.is_grad_enabled() or getattr(args, "train_logit_rows", False)
-                  or getattr(args, "packed_rows", False) or getattr(args, "decoder_rows", False))
+                  or getattr(args, "packed_rows", False) or getattr(args, "decoder_rows", False)
+                  or getattr(args, "finetune_graphs", False))
     if hasattr(model, "engine") and rows_route:
         rows = mask_rows(encoded_ids, tokenizer, args, feed["input_ids"].device)
         return model(logit_rows=rows, **feed)["logits"]
@@ -75,6 +77,8 @@ def train_one_epoch(model, tokenizer, data_loader, optimizer, device, epoch, dat
         model.packed_rows = True  # ragged batches without the padding rows behind each sample's last token (implies the rows route)
     if getattr(args, "decoder_rows", False) and hasattr(model, "decoder_rows"):
         model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
+    if getattr(args, "finetune_graphs", False) and hasattr(model, "finetune_graphs"):
+        model.finetune_graphs = True  # replay the step's forward and backward as two hipGraphs per length bucket (implies the rows route)
     run = EpochRunner(data_loader, args, "Epoch: [{}]".format(epoch), epoch)
     log = LossLog(run, "cls_loss", delayed=getattr(args, "delayed_loss_check", False), reducer=getattr(model, "_reducer", None))
     for i_batch, batch_dict in run:

@@ -16,6 +16,12 @@ Legs of these two workloads:
   rows         args.train_logit_rows: head forward and backward on the [MASK] rows only (logit_rows under autograd)
   rows_packed  args.packed_rows: the same on packed rows (model.packed_rows)
   rows_decoder / rows_packed_decoder   the two above with args.decoder_rows: the enhanced mask decoder on the [MASK] rows only
+  rows_graphs  args.finetune_graphs: the rows route replayed as two hipGraphs per length bucket (model.finetune_graphs); beside
+               it, per leg, `host_ms`: the time the host needs to issue a step (wall clock inside the step call, the device
+               idle in front of it; a pass of its own), and the number of graph captures the run made.  --pad-to-bucket pads the text of every leg to the graphs' length
+               bucket, so that the eager legs run the grid the graphs leg runs
+
+A further `videoqa` shape, `videoqa_short`: B = 32, T = 10, questions of 8 .. 24 tokens (S = 34): the subtitle-free datasets.
 
 A third workload, `mlm`: B = 32, T = 10, ragged text U[32,256] with one sample of 256, labels on 15 % of the non-pad tokens,
 forward with `labels`, backward, clipped FusedAdam; legs `default` and `decoder_rows` (model.decoder_rows).
@@ -42,7 +48,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=20, help="timed iterations per leg (at least 20 for the record)")
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--layers", type=int, default=0, help="encoder layers (0: the xlarge model's 24)")
-ap.add_argument("--only", choices=["videoqa", "mc", "mlm"], default=None)
+ap.add_argument("--only", choices=["videoqa_short", "videoqa", "mc", "mlm"], default=None)
+ap.add_argument("--pad-to-bucket", action="store_true", help="pad the text to a multiple of model.GRAPH_L_BUCKET for every leg")
+ap.add_argument("--legs", default="", help="comma-separated subset of the legs of the videoqa / mc workloads (default: all)")
 a = ap.parse_args()
 dev = torch.device("cuda")
 T, FEAT, MASK = 10, 768, 128000
@@ -62,6 +70,12 @@ def texts(n, lo, hi, seed):
     return ids, tlen
 
 
+def band(t):
+    t = sorted(t)
+    pick = lambda q: round(t[min(len(t) - 1, int(q * len(t)))], 2)
+    return {"median": pick(0.5), "p10": pick(0.1), "p90": pick(0.9), "n": len(t)}
+
+
 def alternate_stats(legs, n, warm):
     """per leg {median, p10, p90} in ms; the legs run in turn inside each iteration"""
     ev = {k: [] for k in legs}
@@ -74,19 +88,31 @@ def alternate_stats(legs, n, warm):
             if it >= warm:
                 ev[k].append((s, e))
     torch.cuda.synchronize()
-    res = {}
-    for k, v in ev.items():
-        t = sorted(s.elapsed_time(e) for s, e in v)
-        pick = lambda q: round(t[min(len(t) - 1, int(q * len(t)))], 2)
-        res[k] = {"median": pick(0.5), "p10": pick(0.1), "p90": pick(0.9), "n": len(t)}
-    return res
+    return {k: band([s.elapsed_time(e) for s, e in v]) for k, v in ev.items()}
+
+
+def host_issue_stats(legs, n):
+    """per leg the host's time to issue a step, in ms: wall clock inside the step call with an idle device in front of it
+    (synchronised before every call, so that neither a full queue nor the step's one read of an input waits for older work);
+    a pass of its own after the device-event pass, which must not be synchronised"""
+    import time
+
+    issue = {k: [] for k in legs}
+    for _ in range(n):
+        for k, f in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            issue[k].append((time.perf_counter() - t0) * 1e3)
+    torch.cuda.synchronize()
+    return {k: band(v) for k, v in issue.items()}
 
 
 def workload(name):
     cfg = DebertaV2Config()
     if a.layers:
         cfg.num_hidden_layers = a.layers
-    n_ans = 1000 if name == "videoqa" else 2
+    n_ans = 2 if name == "mc" else 1000
     torch.manual_seed(0)
     m = DebertaV2ForMaskedLM(cfg, max_feats=T, features_dim=FEAT, ds_factor_attn=8, ds_factor_ff=8, dropout=0.1, n_ans=n_ans)
     m.to(dev).eval()
@@ -95,7 +121,11 @@ def workload(name):
     m.set_answer_embeddings((a2tok * (torch.arange(5)[None] < torch.randint(1, 6, (n_ans, 1), generator=g))).to(dev))
     m.train()
     opt = FusedAdam(m, lr=1e-5)
-    if name == "videoqa":
+    if name == "videoqa_short":
+        B, C = 32, 1
+        ids, tlen = texts(B, 8, 24, seed=5)
+        target = torch.randint(0, n_ans, (B,), generator=g).to(dev)
+    elif name == "videoqa":
         B, C = 32, 1
         ids, tlen = texts(B, 8, 64, seed=2)
         target = torch.randint(0, n_ans, (B,), generator=g).to(dev)
@@ -103,6 +133,9 @@ def workload(name):
         B, C = 8, 4
         ids, tlen = texts(C * B, 64, 502, seed=3)
         target = torch.randint(0, C, (B,), generator=g).to(dev)
+    if a.pad_to_bucket:
+        Lb = min(-(-ids.shape[1] // m.GRAPH_L_BUCKET) * m.GRAPH_L_BUCKET, cfg.max_position_embeddings - T)
+        ids = F.pad(ids, (0, Lb - ids.shape[1]))
     n = ids.shape[0]
     S = T + ids.shape[1]
     vlen = torch.randint(1, T + 1, (B,), generator=g)
@@ -115,9 +148,10 @@ def workload(name):
         args = types.SimpleNamespace(max_feats=T, use_video=True, **opt_in)
         m.packed_rows = bool(opt_in.get("packed_rows"))
         m.decoder_rows = bool(opt_in.get("decoder_rows"))
+        m.finetune_graphs = bool(opt_in.get("finetune_graphs"))
         opt.zero_grad()
         logits = P_vqa.answer_logits(m, Tok, ids, args, **feed)
-        if name == "videoqa":
+        if C == 1:
             loss = F.cross_entropy(logits, target)
         else:
             loss = P_mc.mc_loss(logits.softmax(-1)[:, 0].view(C, B).t(), target, C)
@@ -126,12 +160,20 @@ def workload(name):
 
     legs = {"full": lambda: step(), "rows": lambda: step(train_logit_rows=True), "rows_packed": lambda: step(packed_rows=True),
             "rows_decoder": lambda: step(train_logit_rows=True, decoder_rows=True),
-            "rows_packed_decoder": lambda: step(packed_rows=True, decoder_rows=True)}
+            "rows_packed_decoder": lambda: step(packed_rows=True, decoder_rows=True),
+            "rows_graphs": lambda: step(finetune_graphs=True)}
+    if a.legs:
+        legs = {k: legs[k] for k in a.legs.split(",")}
     res = {"shape": dict(samples=n, S=S, T=T, n_ans=n_ans, candidates=C, layers=cfg.num_hidden_layers, mask_rows=n),
            "rows": {"padded": n * S, "packed": rows_packed, "share": round(rows_packed / (n * S), 3)},
-           "step_ms": alternate_stats(legs, a.steps, a.warmup)}
-    full = res["step_ms"]["full"]["median"]
-    res["speedup_vs_full"] = {k: round(full / v["median"], 3) for k, v in res["step_ms"].items() if k != "full"}
+           "step_ms": alternate_stats(legs, a.steps, a.warmup), "host_ms": host_issue_stats(legs, a.steps),
+           "graph_captures": m.__dict__.get("_finetune_graph_captures", 0),
+           "graph_replays": m.__dict__.get("_finetune_graph_replays", 0)}
+    if "full" in legs:
+        full = res["step_ms"]["full"]["median"]
+        res["speedup_vs_full"] = {k: round(full / v["median"], 3) for k, v in res["step_ms"].items() if k != "full"}
+    if "rows" in legs and "rows_graphs" in legs:
+        res["graphs_vs_rows"] = round(res["step_ms"]["rows"]["median"] / res["step_ms"]["rows_graphs"]["median"], 3)
     del m, opt
     torch.cuda.empty_cache()
     return res
@@ -175,8 +217,8 @@ def workload_mlm():
 out = {"device": torch.cuda.get_device_name(0),
        "method": "device events around forward + loss + backward + clipped FusedAdam, train mode (dropout live); the legs of a workload "
                  f"alternate inside one process; median, 10th and 90th percentile of {a.steps} timed iterations after {a.warmup} "
-                 "warm-up iterations"}
-for w in ("videoqa", "mc"):
+                 "warm-up iterations; host_ms: wall clock the host spends inside the step call, the device idle in front of it, in a pass of its own"}
+for w in ("videoqa_short", "videoqa", "mc"):
     if a.only in (None, w):
         out[w] = workload(w)
 if a.only in (None, "mlm"):
