@@ -90,9 +90,11 @@ def disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk, defer_pos=False):
     row0 = pk_.row0 if pk_ is not None else None  # packed-row layout of q / k / v / dO and of the dQ / dK / dV outputs
     saved_p = getattr(sv, "psave", None) is not None
 
-    # One launch prepares the backward: D_i = dO_i . O_i, the expanded tables PKX (dq) and PQX (dspk), or Q^T / PQ^T (the
-    # key-major shear pass of the recompute route).  (Folding D into kernel A was measured: +43 us there for the O tiles on its
-    # critical path; five separate small launches: 65 us in situ.)
+    # One launch prepares the backward: D_i = dO_i . O_i and the expanded tables PKX (dq) and PQX (dspk) -- the shipped,
+    # saved-P route.  Only the recompute route also gets the transposed copies Q^T / PQ^T (its key-major shear pass reads
+    # them); nothing prepares K^T / Q^T for the position-table gradients any more: fbl_attn_pos_grad reads the token rows of
+    # q / k.  (Folding D into kernel A was measured: +43 us there for the O tiles on its critical path; five separate small
+    # launches: 65 us in situ.)
     Dv = torch.empty(B, nh, S, dtype=F32, device=dev)
     PKX = torch.empty(nh, 2 * Sp, 64, dtype=BF16, device=dev)
     if saved_p:

@@ -1103,6 +1103,10 @@ __global__ __launch_bounds__(128) void attn_bwd_shear_kernel(ShearArgs a) {
 // rows): it walks all samples and their 32-row blocks, every wave keeps the [16 x 64] results of four 16-row tiles of table
 // rows in registers, and the sum over the batch never leaves them: no partial sums, no workspace, deterministic.  The two
 // workgroups of an (execution, head) sit on one XCD (they read the same rows of X).
+// The item loop holds no spilled register and no vector load of a scalar: either one is a vmcnt(0) behind the next item's
+// requests, i.e. a memory round trip per item (1615 -> 1092 us for the pair of launches).  One 8-wave workgroup
+// per (execution, head) with three tiles per wave (X staged once, 600 workgroups) was built and measured at 1359 us: every
+// workgroup walks the same items whatever it owns, and 600 do not fit 512 resident slots either.
 constexpr int PG_MAX_E = 64;  // layer executions per launch (the pointers travel as kernel arguments: capturable)
 struct PosGradArgs {
   const bf16* X[PG_MAX_E];  // dS or dS^T of each execution: [B,nh,Sp,Sp]
@@ -1122,15 +1126,26 @@ constexpr int PG_LDY = 80;   // bf16 row stride of the Y tile (transposing reads
 constexpr int PG_TPW = 4;    // 16-row tiles of table rows per wave
 constexpr int PG_WAVES = 4, PG_THR = PG_WAVES * 64;
 constexpr int PG_ROWS = PG_WAVES * PG_TPW * 16;  // table rows per workgroup
+constexpr int PG_TPR = PG_THR / 32;  // threads per staged row of X
+constexpr int PG_YV = 64 / PG_TPR;    // elements of a staged row of Y per thread
+typedef bf16 pg_yvec __attribute__((ext_vector_type(PG_YV)));
+typedef __attribute__((address_space(4))) const int32_t pg_cint;
+constexpr int PG_NXR_SHORT = 384 / (8 * PG_TPR), PG_NXR_LONG = 512 / (8 * PG_TPR);  // 16-byte chunks per thread: Sp <= 384 / 512
+// the diagonal walk reads, per instruction, 16 consecutive columns (<= 9 banks) of four rows that lie 8 (P + 1) elements apart --
+// 4 banks with P = Sp + 96, so neighbouring k-chunk groups shared half their banks.  Every 8-row group of staged rows is
+// shifted by a further PG_GOFF elements (a multiple of 8: the staging stores stay 16 bytes): the groups start 16 banks apart
+constexpr int PG_GOFF = 24;
 __host__ __device__ constexpr int pg_pitch(int Sp) { return Sp + 2 * PG_PAD; }          // bf16 elements
-__host__ __device__ constexpr int pg_buf(int Sp) { return 32 * pg_pitch(Sp) * 2 + 32 * PG_LDY * 2; }  // one staging buffer
-__host__ __device__ constexpr int pg_smem(int Sp) { return 2 * pg_buf(Sp); }
+constexpr int PG_DD = PG_ROWS * 4;  // bytes of the per-lane delta words behind the staging buffers
+__host__ __device__ constexpr int pg_buf(int Sp) {  // one staging buffer
+  return (32 * pg_pitch(Sp) + 4 * PG_GOFF) * 2 + 32 * PG_LDY * 2;
+}
 
 // CM: upper bound of dcnt (deltas per table row): 3 or 8, chosen from dcnt_max by the launcher (the FrozenBiLM bucket map,
 // position_buckets 256 / max_relative_positions 512, peaks at 6 for S <= 512; maps beyond 8 run pos_grad_wide_kernel)
-// NXR: 16-byte chunks of X per thread and block (Sp / 64); OCC: workgroups per CU the register budget is set for (3: one staging
-// buffer and two barriers per item, 2: two buffers and one barrier)
-template <bool NEG, int CM, int NXR, int OCC>
+// NXR: 16-byte chunks of X per thread and block (Sp / (8 PG_TPR), rounded up); OCC: workgroups per CU the register budget is
+// set for; DB: two staging buffers and one barrier per item (else one buffer and two barriers)
+template <bool NEG, int CM, int NXR, int OCC, bool DB>
 __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1142,28 +1157,34 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
   const int L8 = blockIdx.x >> 3, xcd = blockIdx.x & 7;
   const int prob = (L8 / nsplit) * 8 + xcd, part = L8 % nsplit;
   if (prob >= a.E * a.nh) return;
-  const int e = prob / a.nh, h = prob % a.nh;
-  const int bufsz = pg_buf(Sp);  // two staging buffers: [32][P] rows of X (column PG_PAD + j holds X[row][j]) + [32][PG_LDY] rows of Y
+  // (wave-uniform values the compiler would otherwise keep in vector registers: the budget is tight, and a spilled register's
+  // reload is a vmcnt(0) that also waits for the next item's requests)
+  const int e = __builtin_amdgcn_readfirstlane(prob / a.nh), h = __builtin_amdgcn_readfirstlane(prob % a.nh);
+  const int bufsz = pg_buf(Sp);  // staging buffer(s): [32][P] rows of X (column PG_PAD + j holds X[row][j]) + [32][PG_LDY] rows of Y
   const bf16* X = a.X[e];
   const bf16* Y = a.Y[e];
   const int ntiles = (a.rcnt + 15) / 16;
 
   // this wave's tiles: t = (w + 4 u) * nsplit + part (the parts and the waves take the tiles round-robin: the expensive
-  // log-bucket tiles at both ends of the table and the tiles a short sample touches are spread evenly).  Per tile: the lane's table row, its delta range, and the tile's (wave-uniform) delta span
-  int d0[PG_TPW], dn[PG_TPW], tlo[PG_TPW], thi[PG_TPW];
+  // log-bucket tiles at both ends of the table and the tiles a short sample touches are spread evenly).  Per tile: the tile's
+  // delta span (tlo, thi: scalar registers) and, per lane, the first delta (low half, signed) and the delta count (high half)
+  // of its table row -- kept in LDS behind the staging buffers at [u][w][c]: one 4-byte read per tile and item instead of
+  // PG_TPW registers that would not fit
+  int* ddp = (int*)(smem + (DB ? 2 : 1) * bufsz) + w * 16 + c;
+  int tlo[PG_TPW], thi[PG_TPW];
   bool simple[PG_TPW];
 #pragma unroll
   for (int u = 0; u < PG_TPW; ++u) {
     const int t = (w + PG_WAVES * u) * nsplit + part;
     const int r = min(t * 16 + c, a.rcnt - 1);
     const bool live = t < ntiles && t * 16 + c < a.rcnt;
-    d0[u] = live ? (int)a.dlo[r] : 0;
-    dn[u] = live ? (int)a.dcnt[r] : 0;
+    const int d0 = live ? (int)a.dlo[r] : 0, dn = live ? (int)a.dcnt[r] : 0;
+    ddp[u * PG_WAVES * 16] = (d0 & 0xffff) | (dn << 16);  // (read by this lane only)
     const int rf = min(t * 16, a.rcnt - 1), rl = min(t * 16 + 15, a.rcnt - 1);
-    tlo[u] = t < ntiles ? (int)a.dlo[rf] : 1 << 20;
-    thi[u] = t < ntiles ? (int)a.dlo[rl] + (int)a.dcnt[rl] - 1 : -(1 << 20);
+    tlo[u] = __builtin_amdgcn_readfirstlane(t < ntiles ? (int)a.dlo[rf] : 1 << 20);
+    thi[u] = __builtin_amdgcn_readfirstlane(t < ntiles ? (int)a.dlo[rl] + (int)a.dcnt[rl] - 1 : -(1 << 20));
     // identity band: one delta per row, consecutive rows <-> consecutive deltas (wave-uniform)
-    simple[u] = t < ntiles && t * 16 + 15 < a.rcnt && (thi[u] - tlo[u]) == 15 && __builtin_amdgcn_ballot_w64(dn[u] != 1) == 0;
+    simple[u] = t < ntiles && t * 16 + 15 < a.rcnt && (thi[u] - tlo[u]) == 15 && __builtin_amdgcn_ballot_w64(dn != 1) == 0;
   }
   f32x4 acc[PG_TPW][4];
 #pragma unroll
@@ -1172,63 +1193,82 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
     for (int dt = 0; dt < 4; ++dt) acc[u][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   // the zero columns on both sides are written once (both buffers); the staging rewrites columns [0, Sp) of every row
-  for (int id = tid; id < (OCC >= 3 ? 1 : 2) * 32 * 2 * (PG_PAD / 8); id += PG_THR) {
+  for (int id = tid; id < (DB ? 2 : 1) * 32 * 2 * (PG_PAD / 8); id += PG_THR) {
     const int bsel = id / (32 * 2 * (PG_PAD / 8)), r2 = id % (32 * 2 * (PG_PAD / 8));
     const int row = r2 / (2 * (PG_PAD / 8)), q = r2 % (2 * (PG_PAD / 8));
     const int col = q < PG_PAD / 8 ? q * 8 : PG_PAD + Sp + (q - PG_PAD / 8) * 8;
-    *(bf16x8*)((bf16*)(smem + bsel * bufsz) + row * P + col) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+    *(bf16x8*)((bf16*)(smem + bsel * bufsz) + row * P + (row >> 3) * PG_GOFF + col) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
   }
   const bf16x8 z8 = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-  // staging role of this thread: row tid / 8 of the block, 16-byte chunks (tid % 8) + 8 q  (Sp is a multiple of 64: nq = Sp / 64
-  // chunks per thread; eight consecutive threads fetch 128 contiguous bytes) -- no integer division in the loop
-  const int srow = tid >> 3, sch = tid & 7, nq = Sp >> 6;
+  // staging role of this thread: row tid / PG_TPR of the block, 16-byte chunks (tid % PG_TPR) + PG_TPR q (PG_TPR consecutive
+  // threads fetch 16 PG_TPR contiguous bytes) -- no integer division in the loop.  Y likewise: one chunk of PG_YV elements
+  const int srow = tid / PG_TPR, sch = tid % PG_TPR;
 
   // work list: (sample b, 32-row block k0 < klen[b]) in order; the next item's operands are in flight (registers) during the
-  // current item's arithmetic
-  int b_n = 0, k_n = 0, kl_n = 0;
+  // current item's arithmetic.  The length of the sample AFTER b_n is requested when b_n is entered and first used when it is
+  // left, so no item waits for a scalar load in front of its requests.
+  // klen / row0 are read through the constant address space: scalar loads.  As plain global pointers the compiler read
+  // them with a vector load, a vmcnt(0) and a readfirstlane -- a memory round trip in front of every item's requests
+  const int B = a.B;
+  const pg_cint* klc = (const pg_cint*)a.klen;
+  const pg_cint* r0c = (const pg_cint*)a.row0;
+  auto klen_raw = [&](int b) { return b < B ? (klc ? klc[b] : S) : 0; };
+  int b_n = 0, k_n = 0, kl_n = min(klen_raw(0), S), kl_x = klen_raw(1);
   auto seek = [&]() {  // first item at or after (b_n, k_n)
-    while (b_n < a.B) {
-      kl_n = a.klen ? min(a.klen[b_n], S) : S;
-      if (k_n < kl_n) return true;
+    while (b_n < B && k_n >= kl_n) {
       ++b_n; k_n = 0;
+      kl_n = min(kl_x, S);
+      kl_x = klen_raw(b_n + 1);
     }
-    return false;
+    return b_n < B;
   };
-  bf16x8 rx[NXR], ry;
-  int it_b = 0, it_k = 0, it_kl = 0;
-  auto load_item = [&]() {  // loads item (b_n, k_n) and advances the iterator
-    it_b = b_n; it_k = k_n; it_kl = kl_n;
+  bf16x8 rx[NXR];
+  pg_yvec ry;
+  int it_k = 0, it_kl = 0;
+  // requests item (b_n, k_n) and advances the iterator.  Unconditional: past the last item (b_n = B, kl_n = 0) and for the
+  // chunks beyond kl64 the address is clamped onto a chunk this thread's row group requests anyway (nothing new is fetched)
+  // and the value is replaced by zero -- the requests are never behind a branch that the fragment walk would have to join
+  auto load_item = [&]() {
+    it_k = k_n; it_kl = kl_n;
     const int kl64 = (kl_n + 63) & ~63;  // kernel A wrote the tile pairs below it; anything beyond is unwritten memory
-    const long rb = a.row0 ? (long)a.row0[b_n] : (long)b_n * S;
-    const int lim = a.row0 ? min(a.row0[b_n + 1] - a.row0[b_n], S) : S;
-    const bf16* Xb = X + (((long)b_n * a.nh + h) * Sp) * Sp + (long)k_n * Sp;
-    const bf16* xr = Xb + (long)srow * Sp + sch * 8;
+    const int bb = min(b_n, B - 1);
+    const bf16* xr = X + (((long)bb * a.nh + h) * Sp + k_n + srow) * Sp;
 #pragma unroll
-    for (int q = 0; q < NXR; ++q) rx[q] = (q < nq && sch * 8 + q * 64 < kl64) ? *(const bf16x8*)(xr + q * 64) : z8;
+    for (int q = 0; q < NXR; ++q) {
+      const int col = (sch + PG_TPR * q) * 8;
+      const bool ok = col < kl64;  // (kl64 <= Sp)
+      const bf16x8 v = *(const bf16x8*)(xr + (ok ? col : (sch & 7) * 8));
+      rx[q] = ok ? v : z8;
+    }
     {
+      const long rb = r0c ? (long)r0c[bb] : (long)bb * S;
+      const int lim = r0c ? min(r0c[bb + 1] - r0c[bb], S) : S;
       const int pos = k_n + srow;
-      ry = (pos < lim) ? *(const bf16x8*)(Y + (rb + pos) * a.ldy + h * 64 + sch * 8) : z8;
+      const bf16* yb = Y + rb * a.ldy + h * 64;  // (scalar base + a 32-bit offset per lane: pos < 512, ldy < 2^21)
+      ry = (pos < lim) ? *(const pg_yvec*)(yb + (unsigned)pos * (unsigned)a.ldy + sch * PG_YV) : pg_yvec{};
     }
     k_n += 32;
   };
   int pb = 0;
   bool have = seek();
-  if (have) load_item();
+  load_item();
   while (have) {
     bf16* xs = (bf16*)(smem + pb * bufsz);
-    bf16* ys = xs + 32 * P;
-    if (OCC >= 3) __syncthreads();  // single buffer: the previous item's fragments are read
+    bf16* ys = xs + 32 * P + 4 * PG_GOFF;
+    if (!DB) __syncthreads();  // single buffer: the previous item's fragments are read
     {
-      bf16* xw = xs + srow * P + PG_PAD + sch * 8;
+      bf16* xw = xs + srow * P + (srow >> 3) * PG_GOFF + PG_PAD;
 #pragma unroll
-      for (int q = 0; q < NXR; ++q)
-        if (q < nq) *(bf16x8*)(xw + q * 64) = rx[q];
+      for (int q = 0; q < NXR; ++q) {
+        const int col = (sch + PG_TPR * q) * 8;
+        if (col < Sp) *(bf16x8*)(xw + col) = rx[q];
+      }
     }
-    *(bf16x8*)(ys + srow * PG_LDY + sch * 8) = ry;
+    *(pg_yvec*)(ys + srow * PG_LDY + sch * PG_YV) = ry;
     const int k0 = it_k, kl = it_kl;
     __syncthreads();  // one barrier per item: the buffer written two items from now was read one item ago, before this barrier
     have = seek();
-    if (have) load_item();
+    load_item();
     // Y^T fragments (MFMA A operand: rows d = dt*16 + c, k = the 32 staged rows): transposing reads of the row-major tile
     bf16x8 yf[4];
 #pragma unroll
@@ -1247,8 +1287,10 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
       if (cmax < 0 || cmin >= kl) continue;  // (wave-uniform)
       bf16x8 gf;
       // G[r][k] = sum_t X[k][k -+ (d0 + t)]: lane (table row c, k chunk g) walks diagonals of the staged rows
-      const bf16* xrow = xs + (g * 8) * P + PG_PAD;
-      const int cb = NEG ? (k0 + g * 8 + d0[u]) : (k0 + g * 8 - d0[u]);  // column of row g*8 (q = 0, t = 0)
+      const bf16* xrow = xs + (g * 8) * P + g * PG_GOFF + PG_PAD;  // staged rows g*8 .. g*8 + 7
+      const int dd = ddp[u * PG_WAVES * 16];
+      const int d0 = (int)(int16_t)dd, dn = dd >> 16;
+      const int cb = NEG ? (k0 + g * 8 + d0) : (k0 + g * 8 - d0);  // column of row g*8 (q = 0, t = 0)
       if (simple[u]) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) gf[q] = xrow[q * P + cb + q];
@@ -1256,23 +1298,28 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
         // log buckets (a few deltas per row, <= a.cmax) and edge tiles: columns are clamped into the zero margins
         // (all 8 x CM reads are issued before the first one is used: a read-use-read chain costs an LDS latency per element)
         const int lo = -PG_PAD, hi = Sp + PG_PAD - 1;
-        bf16 vv[8][CM];
+        // (in two halves of four staged rows: the reads of a half are in registers together)
 #pragma unroll
-        for (int q = 0; q < 8; ++q)
+        for (int qh = 0; qh < 8; qh += 4) {
+          bf16 vv[4][CM];
 #pragma unroll
-          for (int t2 = 0; t2 < CM; ++t2) vv[q][t2] = xrow[q * P + clampi(NEG ? cb + q + t2 : cb + q - t2, lo, hi)];
+          for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          float sum = 0.f;
+            for (int t2 = 0; t2 < CM; ++t2)
+              vv[q][t2] = xrow[(qh + q) * P + clampi(NEG ? cb + qh + q + t2 : cb + qh + q - t2, lo, hi)];
 #pragma unroll
-          for (int t2 = 0; t2 < CM; ++t2) sum += t2 < dn[u] ? bf2f(vv[q][t2]) : 0.f;
-          gf[q] = f2bf(sum);
+          for (int q = 0; q < 4; ++q) {
+            float sum = 0.f;
+#pragma unroll
+            for (int t2 = 0; t2 < CM; ++t2) sum += t2 < dn ? bf2f(vv[q][t2]) : 0.f;
+            gf[qh + q] = f2bf(sum);
+          }
         }
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) acc[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(yf[dt], gf, acc[u][dt], 0, 0, 0);
     }
-    if (OCC < 3) pb ^= 1;
+    if (DB) pb ^= 1;
   }
   // lane: table row t*16 + c, columns d = dt*16 + g*4 .. +3
   float* ob = a.out + ((long)e * a.nh + h) * a.rcnt * 64;
@@ -1296,17 +1343,18 @@ __global__ __launch_bounds__(PG_THR, OCC) void pos_grad_kernel(PosGradArgs a) {
 // = 65 KB at Sp = 512) and two barriers per item, two workgroups per CU.  Deterministic: fixed summation order, no atomics.
 constexpr int PGW_PAD = 6;  // fp32 row pitch Sp + 6: C_k(j) at k * pitch + 1 + j, pairs (j odd, j + 1) 8-byte aligned; the 8
                             // rows a lane group walks start 16 banks apart
+constexpr int PGW_TPW = 4, PGW_WAVES = 4, PGW_THR = PGW_WAVES * 64, PGW_ROWS = PGW_WAVES * PGW_TPW * 16;  // its own work split
 __host__ __device__ constexpr int pgw_pitch(int Sp) { return Sp + PGW_PAD; }
 __host__ __device__ constexpr int pgw_smem(int Sp) { return 32 * pgw_pitch(Sp) * 4 + 32 * PG_LDY * 2; }
 
 template <bool NEG>
-__global__ __launch_bounds__(PG_THR, 2) void pos_grad_wide_kernel(PosGradArgs a) {
+__global__ __launch_bounds__(PGW_THR, 2) void pos_grad_wide_kernel(PosGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 15, g = lane >> 4;
   const int S = a.S, Sp = a.Sp, PP = pgw_pitch(Sp);
-  const int nsplit = (a.rcnt + PG_ROWS - 1) / PG_ROWS;
+  const int nsplit = (a.rcnt + PGW_ROWS - 1) / PGW_ROWS;
   const int L8 = blockIdx.x >> 3, xcd = blockIdx.x & 7;
   const int prob = (L8 / nsplit) * 8 + xcd, part = L8 % nsplit;
   if (prob >= a.E * a.nh) return;
@@ -1317,10 +1365,10 @@ __global__ __launch_bounds__(PG_THR, 2) void pos_grad_wide_kernel(PosGradArgs a)
   const bf16* Y = a.Y[e];
   const int ntiles = (a.rcnt + 15) / 16;
 
-  int d0[PG_TPW], dn[PG_TPW], tlo[PG_TPW], thi[PG_TPW];
+  int d0[PGW_TPW], dn[PGW_TPW], tlo[PGW_TPW], thi[PGW_TPW];
 #pragma unroll
-  for (int u = 0; u < PG_TPW; ++u) {
-    const int t = (w + PG_WAVES * u) * nsplit + part;
+  for (int u = 0; u < PGW_TPW; ++u) {
+    const int t = (w + PGW_WAVES * u) * nsplit + part;
     const int r = min(t * 16 + c, a.rcnt - 1);
     const bool live = t < ntiles && t * 16 + c < a.rcnt;
     d0[u] = live ? (int)a.dlo[r] : 0;
@@ -1329,9 +1377,9 @@ __global__ __launch_bounds__(PG_THR, 2) void pos_grad_wide_kernel(PosGradArgs a)
     tlo[u] = t < ntiles ? (int)a.dlo[rf] : 1 << 20;
     thi[u] = t < ntiles ? (int)a.dlo[rl] + (int)a.dcnt[rl] - 1 : -(1 << 20);
   }
-  f32x4 acc[PG_TPW][4];
+  f32x4 acc[PGW_TPW][4];
 #pragma unroll
-  for (int u = 0; u < PG_TPW; ++u)
+  for (int u = 0; u < PGW_TPW; ++u)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) acc[u][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
@@ -1408,7 +1456,7 @@ __global__ __launch_bounds__(PG_THR, 2) void pos_grad_wide_kernel(PosGradArgs a)
     }
     const float* crow = cs + (g * 8) * PP + 1;  // C of staged row g*8 + q: crow[q * PP + j]
 #pragma unroll
-    for (int u = 0; u < PG_TPW; ++u) {
+    for (int u = 0; u < PGW_TPW; ++u) {
       const int cmin = NEG ? k0 + tlo[u] : k0 - thi[u];
       const int cmax = NEG ? k0 + 31 + thi[u] : k0 + 31 - tlo[u];
       if (cmax < 0 || cmin >= kl) continue;  // (wave-uniform)
@@ -1429,8 +1477,8 @@ __global__ __launch_bounds__(PG_THR, 2) void pos_grad_wide_kernel(PosGradArgs a)
   }
   float* ob = a.out + ((long)e * a.nh + h) * a.rcnt * 64;
 #pragma unroll
-  for (int u = 0; u < PG_TPW; ++u) {
-    const int r = ((w + PG_WAVES * u) * nsplit + part) * 16 + c;
+  for (int u = 0; u < PGW_TPW; ++u) {
+    const int r = ((w + PGW_WAVES * u) * nsplit + part) * 16 + c;
     if (r < a.rcnt) {
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) *(f32x4*)(ob + (long)r * 64 + dt * 16 + g * 4) = acc[u][dt];
@@ -1554,17 +1602,21 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
                                  int B, int S, int Sp, int nh, int rcnt, void* stream) {
   if (!grid_shape_ok(S, Sp) || rcnt < 1 || rcnt > 1024) return FBL_ERR_SHAPE;
   if (ldy % 8) return FBL_ERR_ALIGN;
+  if (ldy < 64 || ldy >= (1 << 21)) return FBL_ERR_SHAPE;
   if (!X || !Y || !dlo || !dcnt || !out || dcnt_max < 1) return FBL_ERR_ARG;
   if (row0 && !klen) return FBL_ERR_ARG;
   if (E <= 0 || B <= 0 || nh <= 0) return 0;
   for (int e = 0; e < E; ++e)
     if (!X[e] || !Y[e]) return FBL_ERR_ARG;
-  // three workgroups per CU (one staging buffer) where the rows are short enough for five chunks per thread, two otherwise
-  static const int occ_sw = FBL_ENV_INT("FBL_POSGRAD_OCC", 3);
-  const bool occ3 = Sp <= 320 && dcnt_max <= 3 && occ_sw >= 3;
-  // more than 8 deltas on a table row: the prefix-difference kernel (its own LDS budget)
+  // more than 8 deltas on a table row: the prefix-difference kernel (its own LDS budget and work split)
   const bool wide = dcnt_max > 8;
-  const int nsplit = (rcnt + PG_ROWS - 1) / PG_ROWS;
+  const int nsplit = (rcnt + (wide ? PGW_ROWS : PG_ROWS) - 1) / (wide ? PGW_ROWS : PG_ROWS);
+  // three workgroups per CU (one staging buffer, two barriers per item) where the rows are short enough for five chunks per
+  // thread; two otherwise, with two staging buffers (one barrier per item) while two workgroups' pairs fit the CU's LDS
+  const bool occ3 = Sp <= 320 && dcnt_max <= 3;
+  const bool db = Sp <= 384;
+  static_assert(2 * (2 * pg_buf(384) + PG_DD) <= 160 * 1024, "two double-buffered workgroups per CU");
+  static_assert(PG_TPR * 8 * PG_NXR_LONG >= 512 && PG_TPR * 8 * PG_NXR_SHORT >= 384, "chunks per thread cover the row");
   for (int e0 = 0; e0 < E; e0 += PG_MAX_E) {
     PosGradArgs a{};
     const int ne = E - e0 < PG_MAX_E ? E - e0 : PG_MAX_E;
@@ -1575,13 +1627,16 @@ extern "C" int fbl_attn_pos_grad(int neg, const void* const* X, const void* cons
     a.ldy = ldy; a.dlo = dlo; a.dcnt = dcnt; a.klen = klen; a.row0 = row0;
     a.out = out + (long)e0 * nh * rcnt * 64;
     a.E = ne; a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.rcnt = rcnt; a.cmax = dcnt_max;
-    const dim3 grid((unsigned)(((ne * nh + 7) / 8) * 8 * nsplit)), block(PG_THR);
+    const dim3 grid((unsigned)(((ne * nh + 7) / 8) * 8 * nsplit)), block(wide ? PGW_THR : PG_THR);
     const int rc = fbl_bool(neg != 0, [&](auto NEG) {
       constexpr bool N = decltype(NEG)::value;
       if (wide) return fbl_launch<pos_grad_wide_kernel<N>>(grid, block, pgw_smem(Sp), stream, a);
-      if (occ3) return fbl_launch<pos_grad_kernel<N, 3, 5, 3>>(grid, block, pg_buf(Sp), stream, a);
-      if (dcnt_max <= 3) return fbl_launch<pos_grad_kernel<N, 3, 8, 2>>(grid, block, pg_smem(Sp), stream, a);
-      return fbl_launch<pos_grad_kernel<N, 8, 8, 2>>(grid, block, pg_smem(Sp), stream, a);
+      if (occ3) return fbl_launch<pos_grad_kernel<N, 3, 5, 3, false>>(grid, block, pg_buf(Sp) + PG_DD, stream, a);
+      if (dcnt_max <= 3)
+        return db ? fbl_launch<pos_grad_kernel<N, 3, PG_NXR_SHORT, 2, true>>(grid, block, 2 * pg_buf(Sp) + PG_DD, stream, a)
+                  : fbl_launch<pos_grad_kernel<N, 3, PG_NXR_LONG, 2, false>>(grid, block, pg_buf(Sp) + PG_DD, stream, a);
+      return db ? fbl_launch<pos_grad_kernel<N, 8, PG_NXR_SHORT, 2, true>>(grid, block, 2 * pg_buf(Sp) + PG_DD, stream, a)
+                : fbl_launch<pos_grad_kernel<N, 8, PG_NXR_LONG, 2, false>>(grid, block, pg_buf(Sp) + PG_DD, stream, a);
     });
     if (rc) return rc;
   }
