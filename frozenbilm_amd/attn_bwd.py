@@ -22,6 +22,9 @@ import torch
 from . import lib as L
 
 BF16, F32 = torch.bfloat16, torch.float32
+# softmax scale of the disentangled attention: head dimension 64, three score terms (content-content, content-position,
+# position-content; model/deberta.py:769-776: 1 / sqrt(d * scale_factor))
+ATTN_SCALE = 1.0 / math.sqrt(64 * 3)
 
 
 _RANGE = {}
@@ -85,7 +88,7 @@ def disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk, defer_pos=False):
     # This is also the kernel-level entry that the kernel tests and tools/pmc_attn.py drive with bare stand-ins for `run` and
     # `sv` (B, S, p_att, mask_i32, klen / qkv, pqk, ctx, lse, seed_att): what only an engine step carries is optional here.
     klen, border = run.klen, getattr(run, "border", None)
-    scale = 1.0 / math.sqrt(64 * 3)
+    scale = ATTN_SCALE
     pk_ = getattr(run, "pk", None)
     row0 = pk_.row0 if pk_ is not None else None  # packed-row layout of q / k / v / dO and of the dQ / dK / dV outputs
     saved_p = getattr(sv, "psave", None) is not None

@@ -463,6 +463,21 @@ int qr_check(const QrArgs& a) {
   return 0;
 }
 
+// what the forward and the backward entry point take alike: the operands of the scores, the dropout seed, the shape
+QrArgs qr_inputs(const void* q, int64_t ldq, const int32_t* rseg, const int32_t* rpos, int R, const void* k, int64_t ldk, const void* v,
+                 int64_t ldv, const void* pk, const void* pq, int64_t ldp, const int16_t* relidx, const int32_t* mask,
+                 const int32_t* klen, const int32_t* row0, float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev, int B,
+                 int S, int Sp, int nh, int span2) {
+  QrArgs a{};
+  a.q = (const bf16*)q; a.ldq = ldq; a.rseg = rseg; a.rpos = rpos; a.R = R;
+  a.k = (const bf16*)k; a.ldk = ldk; a.v = (const bf16*)v; a.ldv = ldv;
+  a.pk = (const bf16*)pk; a.pq = (const bf16*)pq; a.ldp = ldp;
+  a.relidx = relidx; a.mask = mask; a.klen = klen; a.row0 = row0;
+  a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
+  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2;
+  return a;
+}
+
 template <bool BWD>
 int qr_launch_rows(const QrArgs& a, hipStream_t st) {
   // an upper bound of the number of 16-row groups that needs no look at rseg: sum_b ceil(n_b / 16) <= R / 16 + B
@@ -477,14 +492,9 @@ extern "C" int fbl_disent_attn_fwd_qrows(const void* q, int64_t ldq, const int32
                                          const int16_t* relidx, const int32_t* mask, const int32_t* klen, const int32_t* row0,
                                          float scale, float p_drop, uint64_t seed, const uint64_t* seed_dev, void* ctx, int64_t ldo,
                                          float* lse, int B, int S, int Sp, int nh, int span2, void* stream) {
-  QrArgs a{};
-  a.q = (const bf16*)q; a.ldq = ldq; a.rseg = rseg; a.rpos = rpos; a.R = R;
-  a.k = (const bf16*)k; a.ldk = ldk; a.v = (const bf16*)v; a.ldv = ldv;
-  a.pk = (const bf16*)pk; a.pq = (const bf16*)pq; a.ldp = ldp;
-  a.relidx = relidx; a.mask = mask; a.klen = klen; a.row0 = row0;
-  a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
+  QrArgs a = qr_inputs(q, ldq, rseg, rpos, R, k, ldk, v, ldv, pk, pq, ldp, relidx, mask, klen, row0, scale, p_drop, seed, seed_dev, B, S,
+                       Sp, nh, span2);
   a.ctx = (bf16*)ctx; a.ldo = ldo; a.lse = lse;
-  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2;
   if (int e = qr_check(a)) return e;
   if (B <= 0 || nh <= 0 || R == 0) return 0;
   return qr_launch_rows<false>(a, (hipStream_t)stream);
@@ -502,17 +512,12 @@ extern "C" int fbl_disent_attn_bwd_qrows(const void* q, int64_t ldq, const int32
                                          float p_drop, uint64_t seed, const uint64_t* seed_dev, void* dQ, int64_t lddq, void* dK,
                                          int64_t lddk, void* dV, int64_t lddv, float* dPK, float* dPQ, int rmin, int rcnt, void* ws,
                                          int64_t ws_bytes, int B, int S, int Sp, int nh, int span2, void* stream) {
-  QrArgs a{};
-  a.q = (const bf16*)q; a.ldq = ldq; a.rseg = rseg; a.rpos = rpos; a.R = R;
-  a.k = (const bf16*)k; a.ldk = ldk; a.v = (const bf16*)v; a.ldv = ldv;
-  a.pk = (const bf16*)pk; a.pq = (const bf16*)pq; a.ldp = ldp;
-  a.relidx = relidx; a.mask = mask; a.klen = klen; a.row0 = row0;
-  a.scale = scale; a.p_drop = p_drop; a.seed = seed; a.seed_dev = seed_dev;
+  QrArgs a = qr_inputs(q, ldq, rseg, rpos, R, k, ldk, v, ldv, pk, pq, ldp, relidx, mask, klen, row0, scale, p_drop, seed, seed_dev, B, S,
+                       Sp, nh, span2);
   a.ctx = (bf16*)O; a.ldo = ldo; a.lse = (float*)lse;
   a.dO = (const bf16*)dO; a.lddo = lddo;
   a.dQ = (bf16*)dQ; a.lddq = lddq; a.dK = (bf16*)dK; a.lddk = lddk; a.dV = (bf16*)dV; a.lddv = lddv;
   a.dPK = dPK; a.dPQ = dPQ; a.rmin = rmin; a.rcnt = rcnt;
-  a.B = B; a.S = S; a.Sp = Sp; a.nh = nh; a.span2 = span2;
   if (int e = qr_check(a)) return e;
   if ((lddo % 8) || (lddq % 8) || (lddk % 8) || (lddv % 8)) return FBL_ERR_ALIGN;
   if (mis16(dO) || mis16(dQ) || mis16(dK) || mis16(dV) || mis16(ws)) return FBL_ERR_ALIGN;

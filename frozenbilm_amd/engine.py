@@ -11,7 +11,6 @@ on the fly, so the fp32 normalised tensor is never written to HBM, and ``t`` dou
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
@@ -19,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .attn_bwd import ATTN_SCALE, _relidx_range, disent_attn_bwd, pos_chain_buffers, pos_table_grads_batched
 from .model.relpos import rel_index_vector
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -671,11 +671,16 @@ class Engine:
             self._pos_cache[li] = c
         return c
 
+    def _pos_cache_allowed(self, run) -> bool:
+        """an inference forward (no gradient bookkeeping, no position dropout) inside model.weights_frozen(), and not the capture
+        of an inference graph: the position projections of a layer may come from _pos_proj_cached"""
+        return not run.save and run.p_hid == 0 and getattr(self.m, "_weights_frozen", 0) > 0 and not self._no_pos_cache
+
     def _layer_fwd(self, run, li: int, kv: Stream, q: Optional[Stream], Rb: torch.Tensor):
         """One execution of encoder layer ``li`` (model/deberta.py:351-375); q != None is the EMD form where the
         query stream (and the attention residual, :290-292) differs from the key/value stream."""
         W = self.Lw[li]
-        B, S, H, I, nh = run.B, run.S, self.H, self.I, self.nh
+        B, S, H, nh = run.B, run.S, self.H, self.nh
         N = run.N
         Sp = _ru(S, 64)
         dev = self.dev
@@ -698,8 +703,7 @@ class Engine:
         #  * the second pass of the enhanced mask decoder projects the SAME key/value stream with the same weights as the
         #    first (model/deberta.py:1395-1408): only its query projection is new, written over the first pass's Q columns.
         infer = not run.save and run.p_hid == 0
-        pqk_c = (self._pos_proj_cached(li, W, Rb)
-                 if infer and getattr(self.m, "_weights_frozen", 0) > 0 and not self._no_pos_cache else None)
+        pqk_c = self._pos_proj_cached(li, W, Rb) if self._pos_cache_allowed(run) else None
         reuse = infer and q is not None and run.emd_qkv is not None
         if reuse:
             qkv = run.emd_qkv
@@ -735,35 +739,49 @@ class Engine:
             psave = torch.empty(B, nh, Sp, Sp, dtype=BF16, device=dev)
             msave = torch.empty(B, nh, Sp // 64, S, dtype=F32, device=dev)
         L.disent_attn_fwd(qkv[:N, :H], qkv[:N, H:2 * H], qkv[:N, 2 * H:], pk, pq, self.relidx(S), run.mask_i32,
-                          1.0 / math.sqrt(64 * 3), ctx, lse, B, S, Sp, nh, self.span2, p_drop=run.p_att,
-                          seed=sv.seed_att, klen=run.klen, border=run.border, lin=self.lin_span,
-                          row0=run.pk.row0 if run.pk is not None else None, psave=psave, msave=msave)
+                          ATTN_SCALE, ctx, lse, B, S, Sp, nh, self.span2, p_drop=run.p_att, seed=sv.seed_att, klen=run.klen,
+                          border=run.border, lin=self.lin_span, row0=run.row0, psave=psave, msave=msave)
         sv.psave, sv.msave = psave, msave
         if run.want_attn and q is None:
             # output_attentions=True: the encoder layers' probabilities (model/deberta.py:544-560; the enhanced-mask-decoder
             # passes are called with return_att=False, :1395-1408), materialised by a plain kernel from the stored lse
             probs = torch.empty(B, nh, S, S, dtype=F32, device=dev)
             L.disent_attn_probs(qkv[:N, :H], qkv[:N, H:2 * H], pk, pq, self.relidx(S), run.mask_i32, lse,
-                                1.0 / math.sqrt(64 * 3), probs, B, S, nh)
+                                ATTN_SCALE, probs, B, S, nh)
             run.attn_out.append(probs)
-        # attention output: dense -> adapter -> dropout -> LN(. + residual)   (:254-260)
-        a1, a2 = self.sites[li]
+        if run.save:
+            sv.qkv, sv.pqk, sv.ctx, sv.lse = qkv[:N], qkv[N:, : 2 * H], ctx, lse  # (run.save: never the inference shortcuts)
+        return self._layer_tail(run, li, sv, ctx, q if q is not None else kv, N, tail=self.span2)
+
+    def _layer_tail(self, run, li: int, sv: "LayerSave", ctx, resid: Stream, N: int, tail=0) -> Stream:
+        """Everything behind the attention of one layer execution, on N rows (the token rows, or the selected rows of the
+        decoder): attention output and FFN.  Fills what `sv` keeps of them with their four dropout seeds and, under run.save,
+        puts `sv` on run.layers (the caller has set what its attention keeps).  tail: see Stream.full."""
+        W, (a1, a2) = self.Lw[li], self.sites[li]
         p = f"deberta.encoder.layer.{li}"
+        # attention output: dense -> adapter -> dropout -> LN(. + residual)   (:254-260)
         a, ob, z1, sv.seed_ad1, sv.seed_ln1 = self._dense_adapter_ln(
-            run, li, ctx, W["Wo"], W["bo"], a1, N, p + ".attention.output.LayerNorm", resid=(q if q is not None else kv))
+            run, li, ctx, W["Wo"], W["bo"], a1, N, p + ".attention.output.LayerNorm", resid=resid)
         # FFN: gelu(dense) -> dense -> adapter -> dropout -> LN(. + a)          (:310-313, :328-334)
-        h = torch.empty(N, I, dtype=BF16, device=dev)
-        hpre = torch.empty(N, I, dtype=BF16, device=dev) if run.save else None
+        h = torch.empty(N, self.I, dtype=BF16, device=self.dev)
+        hpre = torch.empty(N, self.I, dtype=BF16, device=self.dev) if run.save else None
         # training: the epilogue stores gelu'(pre) (bf16) next to gelu(pre) so the backward epilogue is a plain multiply
         L.gemm(a.bf16, W["Wi"], bias=W["bi"], act=L.ACT_GELU_GRAD if run.save else L.ACT_GELU, out_bf16=h, out_pre=hpre)
         out, fb, z2, sv.seed_ad2, sv.seed_ln2 = self._dense_adapter_ln(
-            run, li, h, W["Wd"], W["bd"], a2, N, p + ".output.LayerNorm", resid=Stream(bf16=a.bf16, norm=a.norm), tail=self.span2)
+            run, li, h, W["Wd"], W["bd"], a2, N, p + ".output.LayerNorm", resid=Stream(bf16=a.bf16, norm=a.norm), tail=tail)
         if run.save:
-            sv.qkv, sv.pqk, sv.ctx, sv.lse = qkv[:N], qkv[N:, : 2 * H], ctx, lse  # (run.save: never the inference shortcuts)
             sv.ob, sv.z1, sv.ln1 = ob, z1, a.norm
             sv.hpre, sv.fb, sv.z2, sv.ln2 = hpre, fb, z2, out.norm
             run.layers.append(sv)
         return out
+
+    def _skip_tail_seeds(self, run, li: int):
+        """The seeds of a _layer_tail that is not executed (the decoder with no row selected), drawn in its order -- adapter and
+        LayerNorm dropout of the attention output, then of the FFN output: the sites behind it keep their place in the mask stream."""
+        a1, a2 = self.sites[li]
+        for on in (a1 is not None and run.p_ad > 0, run.p_hid > 0, a2 is not None and run.p_ad > 0, run.p_hid > 0):
+            if on:
+                run.next_seed()
 
     def _forward(self, run, input_ids, video, use_ans, want_hidden):
         cfg, H, dev = self.cfg, self.H, self.dev
@@ -850,7 +868,6 @@ class Engine:
         # logits are read after all
         loss_rows = (rows_only is None and run.labels is not None and not run.save and not self.eager_logits
                      and 0 < run.rows.numel() < N)
-        n_all = B * S
         if loss_rows:
             run.head_in_all = q.bf16
             rows_only = run.rows.to(torch.int32)
@@ -861,13 +878,7 @@ class Engine:
                 L.gather_rows_bf16(q.bf16, rows_only, hin)
         hp, hl = self._head_stage(run, hin, N)
         run.head_pre, run.head_norm, run.head_ln_bf16 = hp, hl.norm, hl.bf16
-        if use_ans:
-            Vout, table, bias = self.n_ans, self.Ansb, self.ans_bias
-        else:
-            Vout, table, bias = self.V, self.Eb, self.head_bias
-        ldv = _ru(Vout, 64)
-        run.Vout = Vout
-        run.head_table, run.head_bias, run.ldv = table, bias, ldv
+        Vout, table, bias, ldv = self._head_tables(run, use_ans)
         if run.labels is not None:
             # A loss is asked for: it only needs the labelled rows.  Their logits come from a small GEMM so CE (and the
             # backward) can follow at once; the full [N, V] logits tensor -- an OUTPUT of the reference API that neither
@@ -876,7 +887,7 @@ class Engine:
             rows = run.rows
             run.rows_i32 = rows.to(torch.int32)
             R = rows.numel()
-            run.loss_acc = L.zeros(2, dtype=F32, device=dev)
+            lc = labels_c = None
             if R > 0:
                 if loss_rows:
                     hrows = hl.bf16  # the head already ran on exactly these rows
@@ -886,13 +897,8 @@ class Engine:
                 lc = torch.empty(R, ldv, dtype=F32, device=dev)
                 L.gemm(hrows, table, bias=bias, out_f32=lc, N=Vout)
                 lab_rows = run.label_rows  # (packed rows: `rows` are activation rows, the labels live on the grid)
-                run.labels_c = run.labels[rows if lab_rows is None else lab_rows].contiguous()
-                run.row_lse = torch.empty(R, dtype=F32, device=dev)
-                L.ce_fwd(lc, run.labels_c, Vout, run.row_lse, run.loss_acc)
-                run.logits_c = lc
-            loss_t = run.loss_acc[0] / run.loss_acc[1]  # mean over labelled rows (CrossEntropyLoss, :1483-1488)
-            run.logits = torch.empty(n_all, ldv, dtype=F32, device=dev)
-            run.logits_pending = True
+                labels_c = run.labels[rows if lab_rows is None else lab_rows]
+            loss_t = self._labelled_loss(run, lc, labels_c)
             if self.eager_logits:
                 self.fill_logits(run)
             return run.logits, loss_t
@@ -901,26 +907,50 @@ class Engine:
         run.logits = logits
         return logits, None
 
+    def _head_tables(self, run, use_ans):
+        """The table behind the head of this pass -- the vocabulary, or the answer embeddings -- noted on `run` for fill_logits and
+        the backward.  Returns (Vout, table, bias, ldv)."""
+        if use_ans:
+            Vout, table, bias = self.n_ans, self.Ansb, self.ans_bias
+        else:
+            Vout, table, bias = self.V, self.Eb, self.head_bias
+        ldv = _ru(Vout, 64)
+        run.Vout, run.head_table, run.head_bias, run.ldv = Vout, table, bias, ldv
+        return Vout, table, bias, ldv
+
+    def _labelled_loss(self, run, lc, labels):
+        """The loss of a labelled call, the mean over its labelled rows (CrossEntropyLoss, :1483-1488), from their fp32 logits
+        `lc` [R, ldv] and labels [R] (both None: no row is labelled); keeps what the backward reads of it.  Allocates the
+        [B*S, ldv] logits that the call hands out, filled on first access (fill_logits)."""
+        run.loss_acc = L.zeros(2, dtype=F32, device=self.dev)
+        if lc is not None:
+            run.labels_c = labels.contiguous()
+            run.row_lse = torch.empty(lc.shape[0], dtype=F32, device=self.dev)
+            L.ce_fwd(lc, run.labels_c, run.Vout, run.row_lse, run.loss_acc)
+            run.logits_c = lc
+        run.logits = torch.empty(run.B * run.S, run.ldv, dtype=F32, device=self.dev)
+        run.logits_pending = True
+        return run.loss_acc[0] / run.loss_acc[1]
+
     def _decoder_rows_fwd(self, run, kv: Stream, Rb, use_ans):
         """The enhanced mask decoder, the head and the loss on the selected rows only (model.decoder_rows).  A decoder row
         depends on its own query row and on all of hs[-2] (both passes take keys and values from it; everything behind the
         attention is row-wise), so this is exact.  K|V of hs[-2] are projected once for both passes; per pass the query
         projection runs on the R compact rows and [PQ|PK] on the position table (its own position-dropout seed), the attention
         is fbl_disent_attn_fwd_qrows, and dense / adapter / LayerNorm / FFN run at N = R.  Row-keyed dropout sites key by the
-        compact row.  The order of run.next_seed() calls is that of _layer_fwd."""
+        compact row.  run.next_seed() is called in the order of _layer_fwd: position table, attention, then the sites of
+        _layer_tail (or _skip_tail_seeds)."""
         from .row_plan import plan_query_rows
 
-        H, I, nh, dev, nL = self.H, self.I, self.nh, self.dev, self.nL
+        H, nh, dev = self.H, self.nh, self.dev
         B, S, N = run.B, run.S, run.N
-        li = nL - 1
+        li = self.nL - 1
         W = self.Lw[li]
         pk = run.pk
         pl = plan_query_rows(run.dec_grid, B, S, inv=pk.inv if pk is not None else None)
         run.dec_plan = pl
         R = pl.R
         Sp = _ru(S, 64)
-        a1, a2 = self.sites[li]
-        p = f"deberta.encoder.layer.{li}"
         q = None
         if R:
             # q0 = pos_emb[pos] + hs[-2][rows], materialised for the R selected rows only
@@ -942,17 +972,14 @@ class Engine:
                 sv.seed_pos = run.next_seed()
             sv.seed_att = run.next_seed() if run.p_att > 0 else 0
             if not R:  # nothing selected: no decoder work; the seeds of the remaining sites are drawn as the full route draws them
-                for on in (a1 is not None and run.p_ad > 0, run.p_hid > 0, a2 is not None and run.p_ad > 0, run.p_hid > 0):
-                    if on:
-                        run.next_seed()
+                self._skip_tail_seeds(run, li)
                 continue
             if run.p_hid > 0:
                 Rd = torch.empty(self.span2, H, dtype=BF16, device=dev)
                 L.dropout_f32(run.R32, run.p_hid, sv.seed_pos, out_bf16=Rd)
             else:
                 Rd = Rb
-            infer = not run.save and run.p_hid == 0
-            if infer and getattr(self.m, "_weights_frozen", 0) > 0 and not self._no_pos_cache:
+            if self._pos_cache_allowed(run):
                 pqk = self._pos_proj_cached(li, W, Rb)
             else:
                 pqk = torch.empty(self.span2, 2 * H, dtype=BF16, device=dev)
@@ -962,28 +989,13 @@ class Engine:
             ctx = torch.empty(R, H, dtype=BF16, device=dev)
             lse = torch.empty(nh, R, dtype=F32, device=dev)
             L.disent_attn_fwd_qrows(qp, pl.rseg, pl.rpos, kvp[:, :H], kvp[:, H:], pqk[:, H:], pqk[:, :H], self.relidx(S), run.mask_i32,
-                                    run.klen, 1.0 / math.sqrt(64 * 3), ctx, lse, B, S, Sp, nh, self.span2, p_drop=run.p_att,
-                                    seed=sv.seed_att, row0=pk.row0 if pk is not None else None)
-            a, ob, z1, sv.seed_ad1, sv.seed_ln1 = self._dense_adapter_ln(
-                run, li, ctx, W["Wo"], W["bo"], a1, R, p + ".attention.output.LayerNorm", resid=q)
-            h = torch.empty(R, I, dtype=BF16, device=dev)
-            hpre = torch.empty(R, I, dtype=BF16, device=dev) if run.save else None
-            L.gemm(a.bf16, W["Wi"], bias=W["bi"], act=L.ACT_GELU_GRAD if run.save else L.ACT_GELU, out_bf16=h, out_pre=hpre)
-            out, fb, z2, sv.seed_ad2, sv.seed_ln2 = self._dense_adapter_ln(
-                run, li, h, W["Wd"], W["bd"], a2, R, p + ".output.LayerNorm", resid=Stream(bf16=a.bf16, norm=a.norm))
+                                    run.klen, ATTN_SCALE, ctx, lse, B, S, Sp, nh, self.span2, p_drop=run.p_att, seed=sv.seed_att,
+                                    row0=run.row0)
             if run.save:
-                sv.qr = dict(q=qp, kv=kvp, pqk=pqk, ctx=ctx, lse=lse)
-                sv.ob, sv.z1, sv.ln1 = ob, z1, a.norm
-                sv.hpre, sv.fb, sv.z2, sv.ln2 = hpre, fb, z2, out.norm
-                run.layers.append(sv)
-            q = out
+                sv.qc, sv.kvp, sv.pqk, sv.ctx, sv.lse = qp, kvp, pqk, ctx, lse
+            q = self._layer_tail(run, li, sv, ctx, q, R)
         # ---- head on the compact rows directly (no gather)
-        if use_ans:
-            Vout, table, bias = self.n_ans, self.Ansb, self.ans_bias
-        else:
-            Vout, table, bias = self.V, self.Eb, self.head_bias
-        ldv = _ru(Vout, 64)
-        run.Vout, run.head_table, run.head_bias, run.ldv = Vout, table, bias, ldv
+        Vout, table, bias, ldv = self._head_tables(run, use_ans)
         hin = q.bf16 if R else torch.empty(0, H, dtype=BF16, device=dev)
         hp, hl = self._head_stage(run, hin, R)
         run.head_pre, run.head_norm, run.head_ln_bf16 = hp, hl.norm, hl.bf16
@@ -995,16 +1007,8 @@ class Engine:
             return run.logits, None
         # labelled call: nonzero() lists the rows in ascending order, which is the compact order
         run.rows_i32 = run.rows.to(torch.int32)
-        run.loss_acc = L.zeros(2, dtype=F32, device=dev)
-        if R:
-            run.labels_c = run.labels[pl.grid].contiguous()
-            run.row_lse = torch.empty(R, dtype=F32, device=dev)
-            L.ce_fwd(lc, run.labels_c, Vout, run.row_lse, run.loss_acc)
-            run.logits_c = lc
-        loss_t = run.loss_acc[0] / run.loss_acc[1]
-        run.logits = torch.empty(B * S, ldv, dtype=F32, device=dev)  # the selected rows, zero elsewhere: filled on first access
-        run.logits_pending = True
-        return run.logits, loss_t
+        loss_t = self._labelled_loss(run, lc, run.labels[pl.grid]) if R else self._labelled_loss(run, None, None)
+        return run.logits, loss_t  # (the logits: the selected rows, zero elsewhere)
 
     def fill_logits(self, run):
         """Full [N, V] logits of a forward that only computed the labelled rows (see _forward); idempotent.  Writes into
@@ -1210,7 +1214,7 @@ class Engine:
             # (25 launches a step).  A buffer returns to the pool when the parked gradient products that read its [dy | dz]
             # blocks have been enqueued (_dw_flush).  Captured steps and the immediate-launch route allocate as before.
             pooled = None
-            can_pool = not torch.cuda.is_current_stream_capturing() and a1.grouped and sv.qr is None  # (one pooled shape: N rows)
+            can_pool = not torch.cuda.is_current_stream_capturing() and a1.grouped and sv.kvp is None  # (one pooled shape: N rows)
             if can_pool and self._dyz_shape != (N, Kf):  # a new batch shape (text padded to the longest sample): one pool, of
                 self._dyz_pool.clear()                           # the current shape only -- never one per shape seen
                 self._dyz_shape = (N, Kf)
@@ -1234,13 +1238,10 @@ class Engine:
             if a1 is not None:
                 do = self._adapter_bwd(run, a1, dy1, sv.z1, sv.ob, sv.seed_ad1)
             L.gemm(do, W["WoT"], out_bf16=dctx)
-        if sv.qr is not None:  # decoder on selected rows: dQ is compact, [dK | dV] covers every key row
-            dqc, dkv = self._attn_bwd_qrows(run, sv, dctx)
-            dq = torch.empty(N, H, dtype=F32, device=dev)
-            L.gemm(dqc, W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
-            return dq, dkv
-        dqkv = self._attn_bwd(run, sv, dctx)
+        if self.reducer is not None:  # ~0.15 ms (0.35 until round 6) without one-workgroup-per-CU GEMM tiles: where gradient collectives may start (DESIGN 6)
+            self.reducer.window()
         if not sv.emd:
+            dqkv = self._attn_bwd(run, sv, dctx)
             dx = torch.empty(N, H, dtype=F32, device=dev)
             L.gemm(dqkv, W["WqkvT"], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dx)
             return dx, None
@@ -1248,19 +1249,18 @@ class Engine:
         # gradient of the query stream and, in place of the key/value-stream gradient, the bf16 [dK | dV] operand it is the
         # product of -- the caller chains both passes' products into ONE accumulator through the GEMM epilogues
         # (dx = dq_first + dkv_second + dkv_first: no stand-alone additions of [N, H] fp32 tensors).
+        if sv.kvp is not None:  # decoder on selected rows: dQ is compact, [dK | dV] covers every key row
+            dq_op, dkv_op = self._attn_bwd_qrows(run, sv, dctx)
+        else:
+            dqkv = self._attn_bwd(run, sv, dctx)
+            dq_op, dkv_op = dqkv[:, :H], dqkv[:, H:]
         dq = torch.empty(N, H, dtype=F32, device=dev)
-        L.gemm(dqkv[:, :H], W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
-        return dq, dqkv[:, H:]
+        L.gemm(dq_op, W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
+        return dq, dkv_op
 
     def _attn_bwd(self, run, sv, dctx):
-        B, S, H, nh = run.B, run.S, self.H, self.nh
-        N = run.N
-        dqkv = torch.empty(N, 3 * H, dtype=BF16, device=self.dev)
-        from .attn_bwd import disent_attn_bwd
-
-        if self.reducer is not None:  # ~0.15 ms (0.35 until round 6) without one-workgroup-per-CU GEMM tiles: where gradient collectives may start (DESIGN 6)
-            self.reducer.window()
-
+        """Backward of the attention of one layer execution on the token rows: the bf16 [dQ | dK | dV] operand [N, 3H]."""
+        dqkv = torch.empty(run.N, 3 * self.H, dtype=BF16, device=self.dev)
         # The position-table gradients of this execution (dPK = G1^T.Q, dPQ = G2^T.K) are NOT formed here: its dS / dS^T and
         # q / k go on the per-step lists, and one chain at the END of backward handles all executions
         # (attn_bwd.pos_table_grads_batched).  ft_ln=False: nothing trainable sits behind the position tables, nothing is kept.
@@ -1272,13 +1272,9 @@ class Engine:
     def _attn_bwd_qrows(self, run, sv, dctx):
         """Backward of the attention of one decoder execution on selected rows (fbl_disent_attn_bwd_qrows): returns dQ bf16
         [R, H] and [dK | dV] bf16 [N, 2H]; its position-table gradients go straight onto the step's chain."""
-        from .attn_bwd import _relidx_range
-
         B, S, H, nh, dev = run.B, run.S, self.H, self.nh, self.dev
-        pl, qr = run.dec_plan, sv.qr
+        pl = run.dec_plan
         R, Sp = pl.R, _ru(S, 64)
-        if self.reducer is not None:
-            self.reducer.window()
         rmin, rcnt = _relidx_range(S, self.cfg)
         dqc = torch.empty(R, H, dtype=BF16, device=dev)
         dkv = torch.empty(run.N, 2 * H, dtype=BF16, device=dev)
@@ -1286,14 +1282,21 @@ class Engine:
         # behind the position table) the table pass is not launched
         dpk, dpq = run.pos_chain.formed_slot() if run.pos_chain is not None else (None, None)
         ws = torch.empty(L.disent_attn_bwd_qrows_ws_bytes(R, Sp, nh), dtype=torch.uint8, device=dev)
-        kvp, pqk = qr["kv"], qr["pqk"]
-        L.disent_attn_bwd_qrows(qr["q"], pl.rseg, pl.rpos, kvp[:, :H], kvp[:, H:], pqk[:, H:], pqk[:, :H], self.relidx(S), run.mask_i32,
-                                run.klen, dctx, qr["ctx"], qr["lse"], 1.0 / math.sqrt(64 * 3), dqc, dkv[:, :H], dkv[:, H:], dpk, dpq,
-                                rmin, rcnt, ws, B, S, Sp, nh, self.span2, p_drop=run.p_att, seed=sv.seed_att,
-                                row0=run.pk.row0 if run.pk is not None else None)
+        kvp, pqk = sv.kvp, sv.pqk
+        L.disent_attn_bwd_qrows(sv.qc, pl.rseg, pl.rpos, kvp[:, :H], kvp[:, H:], pqk[:, H:], pqk[:, :H], self.relidx(S), run.mask_i32,
+                                run.klen, dctx, sv.ctx, sv.lse, ATTN_SCALE, dqc, dkv[:, :H], dkv[:, H:], dpk, dpq,
+                                rmin, rcnt, ws, B, S, Sp, nh, self.span2, p_drop=run.p_att, seed=sv.seed_att, row0=run.row0)
         if run.pos_chain is not None:
             run.pos_chain.add_formed(sv.seed_pos)
         return dqc, dkv
+
+    def _dlog_operand(self, g):
+        """A gradient handed in on logits, g [rows, Vout], as the bf16 [rows, Vp] operand of _head_bwd (padding columns zero)."""
+        rows, Vout = g.shape
+        Vp = _ru(Vout, 64)
+        dlog = torch.zeros(rows, Vp, dtype=BF16, device=self.dev) if Vp != Vout else torch.empty(rows, Vp, dtype=BF16, device=self.dev)
+        dlog[:, :Vout].copy_(g)
+        return dlog
 
     def _head_bwd(self, run, rows, dlog, dq, all_rows=False, compact=False):
         """Backward of the prediction head for the rows `rows` (int32 indices into the N token rows) given their bf16
@@ -1376,31 +1379,23 @@ class Engine:
             rows = run.logit_rows
             R = rows.numel()
             if R > 0:
-                dlog = torch.zeros(R, Vp, dtype=BF16, device=dev) if Vp != Vout else torch.empty(R, Vp, dtype=BF16, device=dev)
+                gl = glogits.reshape(R, Vout)
                 if dec is not None:  # the caller's order -> the compact order
-                    dlog[:, :Vout].copy_(glogits.reshape(R, Vout).index_select(0, dec.order))
-                    self._head_bwd(run, None, dlog, dq, all_rows=True, compact=True)
+                    self._head_bwd(run, None, self._dlog_operand(gl.index_select(0, dec.order)), dq, all_rows=True, compact=True)
                 else:
-                    dlog[:, :Vout].copy_(glogits.reshape(R, Vout))
-                    self._head_bwd(run, rows, dlog, dq, compact=True)
-                del dlog
+                    self._head_bwd(run, rows, self._dlog_operand(gl), dq, compact=True)
         # ---- gradient handed in on the logits themselves (downstream losses): every token row
         elif glogits is not None and dec is not None:
             # decoder on selected rows: out.logits holds the selected rows and constants (zero) elsewhere, so only the gradient
             # handed in at those rows has anything to flow into -- taken at the grid rows in compact order
             if dec.R:
-                dlog = torch.zeros(dec.R, Vp, dtype=BF16, device=dev) if Vp != Vout else torch.empty(dec.R, Vp, dtype=BF16, device=dev)
-                dlog[:, :Vout].copy_(glogits.reshape(B * S, Vout).index_select(0, dec.grid))
-                self._head_bwd(run, None, dlog, dq, all_rows=True, compact=True)
-                del dlog
+                gl = glogits.reshape(B * S, Vout).index_select(0, dec.grid)
+                self._head_bwd(run, None, self._dlog_operand(gl), dq, all_rows=True, compact=True)
         elif glogits is not None:
             gl = glogits.reshape(B * S, Vout)
             if pk is not None:  # (gradients handed in at positions without a row have nothing to flow into)
                 gl = gl.index_select(0, pk.sel)
-            dlog = torch.zeros(N, Vp, dtype=BF16, device=dev) if Vp != Vout else torch.empty(N, Vp, dtype=BF16, device=dev)
-            dlog[:, :Vout].copy_(gl)
-            self._head_bwd(run, torch.arange(N, dtype=torch.int32, device=dev), dlog, dq, all_rows=True)
-            del dlog
+            self._head_bwd(run, torch.arange(N, dtype=torch.int32, device=dev), self._dlog_operand(gl), dq, all_rows=True)
 
         def stage_done(key):  # a stage's gradients are final once the adapter products parked in it have been launched
             run.dw_ready_keys.append(key)
@@ -1409,8 +1404,6 @@ class Engine:
         stage_done("head")
         run.pos_chain = None
         if "deberta.encoder.LayerNorm.weight" in self.G:
-            from .attn_bwd import pos_chain_buffers
-
             run.pos_chain = pos_chain_buffers(self, run)
             if dec is not None:  # the two decoder executions are the first of the chain also when nothing was selected (R = 0:
                 # they were not saved; zero tables keep the chain's order equal to the order of WposT_exec)
@@ -1465,8 +1458,6 @@ class Engine:
         # ---- relative-position LayerNorm (receives grads from every layer execution)
         rn = run.rel_norm
         if run.pos_chain is not None:
-            from .attn_bwd import pos_table_grads_batched
-
             dR = pos_table_grads_batched(self, run, run.pos_chain)
             run.pos_chain = None
             L.ln_bwd(dR, rn.t, rn.stats, rn.gamma, dgamma=self.G.get("deberta.encoder.LayerNorm.weight"),
@@ -1556,7 +1547,9 @@ class LayerSave:
     seed_ln2: int = 0
     psave: torch.Tensor = None
     msave: torch.Tensor = None
-    qr: Optional[dict] = None  # decoder on selected rows: compact q, the shared K|V, [PQ|PK], ctx, lse (see _decoder_rows_fwd)
+    # decoder on selected rows (_decoder_rows_fwd) in place of qkv; pqk, ctx and lse above are then those of its R compact rows
+    qc: Optional[torch.Tensor] = None   # bf16 [R, H]: the projected query of the selected rows
+    kvp: Optional[torch.Tensor] = None  # bf16 [N, 2H]: K|V of hs[-2], shared by both passes; set = a decoder-rows execution
 
 
 @dataclass
@@ -1633,6 +1626,11 @@ class Run:
     def __post_init__(self):
         if not self.N:
             self.N = self.B * self.S
+
+    @property
+    def row0(self) -> Optional[torch.Tensor]:
+        """int32 [B+1] first activation row of every sample as the attention kernels take it: packed rows only, else None"""
+        return self.pk.row0 if self.pk is not None else None
 
     def next_seed(self) -> int:
         self._site += 1

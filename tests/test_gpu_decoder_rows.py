@@ -24,7 +24,8 @@ DEV = "cuda"
 
 def _saved_rows(run):
     """the two decoder executions are the last two saved ones: the row count of what they kept"""
-    return [sv.qr["ctx"].shape[0] for sv in run.layers[-2:]], [sv.ln2.t.shape[0] for sv in run.layers[-2:]]
+    assert all(sv.kvp is not None for sv in run.layers[-2:])
+    return [sv.ctx.shape[0] for sv in run.layers[-2:]], [sv.ln2.t.shape[0] for sv in run.layers[-2:]]
 
 
 def _mlm_model(train):
@@ -245,6 +246,23 @@ def test_nothing_selected_under_gradients():
     assert res[True].keys() == res[False].keys()
     for n in res[False]:
         assert torch.equal(res[True][n], torch.zeros_like(res[True][n])) and torch.equal(res[False][n], res[True][n]), n
+
+
+def test_nothing_selected_with_live_dropout_draws_the_seeds_of_the_full_decoder():
+    """R = 0 in train mode with every dropout probability at its configured non-zero value: the decoder that is not executed
+    draws the seeds of all its sites, so the forward ends at the same place of the mask stream with the option on and off"""
+    cfg = _tiny_cfg()
+    m = build(cfg, O.synth_params(cfg, seed=74, std=0.05, ln_jitter=0.1), train=True)
+    batch = _labelled(cfg, 4, 40, seed=35)
+    batch["labels"] = torch.full_like(batch["labels"], -100)
+    sites = {}
+    for on in (False, True):
+        m.decoder_rows = on
+        run = _forward_at(m, batch, None, step_seed=3)._run
+        assert run.p_hid > 0 and run.p_att > 0 and run.p_ad > 0
+        assert (run.dec_plan is not None) == on and (not on or run.dec_plan.R == 0)
+        sites[on] = run._site
+    assert sites[True] == sites[False] > 0, sites
 
 
 # ------------------------------------------------------------------------------------------------ 3. edges
