@@ -87,7 +87,12 @@ def run_case(L, c, neg):
 
 
 def reference(c, neg):
-    """float64 on the CPU, straight from the definition"""
+    """float64 on the CPU, straight from the definition.  Returns (out, bound): bound is the per-element derived bound of
+    tests/attn_refs.py -- the MFMA operand G[r][k] (the fp32 sum of the <= 8 values of a table row's deltas, or a difference of two
+    fp32 prefix sums of the staged row where a row collects more than 8) is rounded to bf16, the sum over k and over the batch is
+    an fp32 reduction of n = sum_b klen_b exact products:
+        |err| <= (2^-8 + 16 u + 2 n u) sum |G|abs |y|   (+ 96 u sum_k rowabs_k |y_k| for the prefix-difference kernel)"""
+    from tests.attn_refs import G_RND, PREFIX_RND, U
     S, B, kl, rcnt = c["S"], c["B"], c["kl"], c["rcnt"]
     H = NH * 64
     dlo, dcnt = c["dlo"].cpu().long(), c["dcnt"].cpu().long()
@@ -101,6 +106,8 @@ def reference(c, neg):
     delta = (kk[None, :] - kk[:, None]) if neg else (kk[:, None] - kk[None, :])
     R = row_of[delta + S - 1]  # [k, col]
     out = torch.zeros(E, NH, rcnt, 64, dtype=torch.float64)
+    mag = torch.zeros_like(out)
+    wide = torch.zeros(E, NH, 1, 64, dtype=torch.float64)
     for e in range(E):
         x = c["Xs"][neg][e].cpu().double()
         y = c["Ys"][neg][e].cpu().double()[:, neg * H:(neg + 1) * H]
@@ -111,7 +118,13 @@ def reference(c, neg):
             r0 = c["row0_host"][b]
             yb = y[r0:r0 + n].view(n, NH, 64)
             out[e] += torch.einsum("hkr,khd->hrd", G, yb)
-    return out
+            Ga = torch.zeros(NH, n, rcnt, dtype=torch.float64).scatter_add_(2, R[:n, :n].expand(NH, n, n), xb.abs())
+            mag[e] += torch.einsum("hkr,khd->hrd", Ga, yb.abs())
+            wide[e] += torch.einsum("hk,khd->hd", xb.abs().sum(2), yb.abs())[:, None, :]
+    bound = (G_RND + 2 * sum(kl) * U) * mag
+    if c["dmax"] > 8:
+        bound = bound + PREFIX_RND * wide
+    return out, bound
 
 
 @pytest.fixture(scope="module")
@@ -135,7 +148,7 @@ def test_pos_grad(L, name):
     for neg in (0, 1):
         got = run_case(L, c, neg)
         again = run_case(L, c, neg)
-        ref = reference(c, neg)
+        ref, bound = reference(c, neg)
         g = got.cpu().double()
         assert torch.isfinite(g).all(), f"{name} neg={neg}: non-finite results"
         atol = ATOL_REL * ref.abs().max().item()
@@ -143,3 +156,7 @@ def test_pos_grad(L, name):
         print(f"{name} neg={neg}: max |err| {err.max().item():.3e}  max |ref| {ref.abs().max().item():.3e}  atol {atol:.3e}")
         assert torch.allclose(g, ref, rtol=RTOL, atol=atol), f"{name} neg={neg}: max |err| {err.max().item():.3e}, atol {atol:.3e}"
         assert torch.equal(got, again), f"{name} neg={neg}: two identical calls differ"
+        # per element, next to the global bound above: bf16 G operand + fp32 reduction
+        ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))
+        print(f"{name} neg={neg}: worst |err| / derived bound {ratio.max().item():.3f}")
+        assert ratio.max().item() <= 1.0, f"{name} neg={neg}: |err| / bound {ratio.max().item():.3f} at {int(ratio.argmax())}"
