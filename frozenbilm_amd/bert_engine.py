@@ -93,6 +93,15 @@ def bert_packing(mask, labels, logit_rows, B: int, S: int, T: int) -> Optional[P
     return Packing(row0=row0, sel=sel, inv=inv, pos=pos, n=n)
 
 
+def _hid_rows(run, ghid, i):
+    """the gradient handed in on hidden_states[i] as fp32 activation rows [N, H] (packed rows: gathered), or None"""
+    g = ghid[i] if ghid is not None and i < len(ghid) else None
+    if g is None:
+        return None
+    g = g.reshape(run.B * run.S, g.shape[-1]).to(F32)
+    return g.index_select(0, run.pk.sel) if run.pk is not None else g.contiguous()
+
+
 class BertEngine:
     # LayerNorm forward / backward and materialisation work on the same representation as the DeBERTa engine's
     _ln = Engine._ln
@@ -221,13 +230,15 @@ class BertEngine:
     def run(self, input_ids, attention_mask, video, video_mask, labels, mlm, want_hidden, logit_rows=None):
         m = self.m
         train = m.training
-        need_grad = torch.is_grad_enabled() and any(self.named[n].requires_grad for n in self.order)
         if input_ids.device != self.dev:
             raise RuntimeError(f"inputs must be on {self.dev}")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
         B, Lt = input_ids.shape
         use_video = bool(self.F) and video is not None
+        # a `video` that takes a gradient of its own becomes a tensor input of the step's autograd node (as Engine.run does it)
+        grad_in = [("video", video)] if (torch.is_grad_enabled() and use_video and video.requires_grad) else []
+        need_grad = torch.is_grad_enabled() and (bool(grad_in) or any(self.named[n].requires_grad for n in self.order))
         T = video.shape[1] if use_video else 0
         S = T + Lt
         if S > self.cfg.max_position_embeddings:
@@ -278,6 +289,9 @@ class BertEngine:
             run.logit_rows = logit_rows.to(self.dev).to(torch.int32).contiguous().view(-1)
             if pk is not None:
                 run.logit_rows = pk.inv[run.logit_rows.long()].to(torch.int32)
+        run.grad_in = tuple(k for k, _ in grad_in)
+        run.video_dtype = video.dtype if use_video else None
+        run.hid_grad = bool(want_hidden) and need_grad  # the hidden states handed out are outputs of the step's node
         with L.seed_word(None):
             logits, loss_t = self._forward(run, input_ids.contiguous(), video, use_ans, want_hidden)
         Vout = run.Vout
@@ -289,9 +303,13 @@ class BertEngine:
             res["hidden_states"] = run.hidden_out
         if need_grad:
             lt = loss_t if loss_t is not None else torch.zeros((), dtype=F32, device=self.dev)
-            loss_o, logits_o = _StepFn.apply(self, run, lt, res["logits"], *[self.named[n] for n in self.order])
-            res["logits"] = logits_o
+            hid = res["hidden_states"] if run.hid_grad else ()
+            outs = _StepFn.apply(self, run, lt, res["logits"], len(hid), *hid, *[t for _, t in grad_in],
+                                 *[self.named[n] for n in self.order])
+            loss_o, res["logits"] = outs[:2]
             res["loss"] = loss_o if run.labels is not None else None
+            if hid:
+                res["hidden_states"] = tuple(outs[2:])
         elif run.labels is not None:
             res["loss"] = loss_t
         return res
@@ -304,7 +322,7 @@ class BertEngine:
         vproj = None
         if T:
             vb = torch.zeros(B * T, self.Fp, dtype=BF16, device=dev)
-            vb[:, : self.F] = video.reshape(B * T, self.F)
+            vb[:, : self.F] = video.detach().reshape(B * T, self.F)  # (detached: its gradient comes from the step's own backward)
             vproj = torch.empty(B * T, H, dtype=F32, device=dev)
             L.gemm(vb, self._video_weight(), bias=self.P["bert.embeddings.linear_video.bias"], out_f32=vproj)
             run.video_bf16 = vb
@@ -431,7 +449,11 @@ class BertEngine:
         return out
 
     # ------------------------------------------------------------------ backward
-    def backward(self, run, gloss: Optional[torch.Tensor], glogits: Optional[torch.Tensor] = None, attach: bool = True):
+    def backward(self, run, gloss: Optional[torch.Tensor], glogits: Optional[torch.Tensor] = None, attach: bool = True,
+                 ghid=None):
+        """ghid: gradients handed in on the hidden states of an output_hidden_states=True call ([B, S, H] or None each); each is
+        added to the running dx where the backward crosses that boundary.  Returns the gradients of the inputs named in
+        run.grad_in as a dict ("video": [B, T, F] in the caller's dtype)."""
         if not run.save:
             raise RuntimeError("forward was run without gradient bookkeeping")
         H, dev = self.H, self.dev
@@ -440,7 +462,9 @@ class BertEngine:
         if attach:
             self.attach_grads()
         red = self.reducer  # data parallel: told when a stage's bucket is final, where collectives may start, when the step ends
-        if run.logit_rows is not None and run.logit_rows.numel() == 0 and red is None:
+        if ghid is not None and all(g is None for g in ghid):
+            ghid = None
+        if run.logit_rows is not None and run.logit_rows.numel() == 0 and red is None and ghid is None:
             return  # no row was asked for: every gradient is exactly zero, nothing is launched (a reducer still needs its buckets)
         dx = L.zeros(N, H, dtype=F32, device=dev)
         Vout = run.Vout
@@ -466,25 +490,43 @@ class BertEngine:
             dlog[:, :Vout].copy_(gl)
             dx = self._head_bwd(run, None, dlog, dx)
         for li in reversed(range(self.nL)):
+            g = _hid_rows(run, ghid, li + 1)  # handed in on this layer's output
+            if g is not None:
+                dx.add_(g)
             dx = self._layer_bwd(run, li, run.layers[li], dx)
             if red is not None:
                 red.ready(f"layer{li}")
         run.layers.clear()
         # ---- embeddings: post-LN dropout, LayerNorm (dgamma / dbeta), linear_video on the video rows
+        g = _hid_rows(run, ghid, 0)  # hidden_states[0]: the embedding output, behind its dropout
+        if g is not None:
+            dx.add_(g)
         if run.p_hid > 0:
             L.dropout_f32(dx, run.p_hid, run.seed_emb, out_f32=dx)
         dt, dyb = self._ln_bwd("bert.embeddings.LayerNorm", dx, run.emb_norm, 0.0, 0, want_dy_bf16=bool(T))
-        if T and "bert.embeddings.linear_video.weight" in self.G:
+        want_dvideo = "video" in run.grad_in and T
+        if T and ("bert.embeddings.linear_video.weight" in self.G or want_dvideo):
             # the video slots are the first T rows of every sample (packed rows: plen >= T)
             first = torch.arange(B, device=dev, dtype=torch.int32) * S if pk is None else pk.row0[:-1]
             vrows = (first[:, None] + torch.arange(T, device=dev, dtype=torch.int32)[None, :]).view(-1).contiguous()
             dv = torch.empty(B * T, H, dtype=BF16, device=dev)
             L.gather_rows_bf16(dyb, vrows, dv)
+        if T and "bert.embeddings.linear_video.weight" in self.G:
             L.gemm_tn_acc(dv, run.video_bf16, self.G["bert.embeddings.linear_video.weight"], self.sk_ws, M=H, N=self.F)
             L.colsum(dv, self.G["bert.embeddings.linear_video.bias"], self._cs_ws)
         if red is not None:
             red.ready("emb")
             red.finish()
+        gin = {}
+        if want_dvideo:
+            # dvideo = d(embedding rows of the video slots) . W_video: bf16 operands, fp32 accumulation, against the K-contiguous
+            # (transposed) copy of linear_video.weight, which only a step with this gradient builds
+            WvT = torch.empty(self.F, H, dtype=BF16, device=dev)
+            L.transpose_to_bf16(self.P["bert.embeddings.linear_video.weight"], WvT)
+            dvid = torch.empty(B * T, self.Fp, dtype=F32, device=dev)
+            L.gemm(dv, WvT, out_f32=dvid, N=self.F)
+            gin["video"] = dvid[:, : self.F].reshape(B, T, self.F).to(run.video_dtype)
+        return gin
 
     def _head_bwd(self, run, rows, dlog, dx, compact=False):
         """dx[rows] += d/d(head input) for the bf16 logit gradients dlog [R, Vp] of those rows (rows None: every row); returns dx.

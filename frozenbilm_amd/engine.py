@@ -284,7 +284,9 @@ class Engine:
             self.Lw.append(d)
         # [Wq ; Wk]^T of every layer EXECUTION that has a backward, in backward order (the last layer's two enhanced-mask-decoder
         # passes, then layers nL-2 .. 0): the position-table gradients of all of them are projected by one strided-batch GEMM
-        order = [nL - 1, nL - 1] + list(range(nL - 2, -1, -1))
+        # (behind them the last layer once more: its own encoder execution, which has a backward only when a gradient arrives on
+        # hidden_states[nL]; it joins the chain last, so every other step takes the first nL + 1 entries as before)
+        order = [nL - 1, nL - 1] + list(range(nL - 2, -1, -1)) + [nL - 1]
         self.WposT_exec = torch.empty(len(order), H, 2 * H, dtype=BF16, device=dev)
         for e, li in enumerate(order):
             self.WposT_exec[e].copy_(self.Lw[li]["WqkvT"][:, : 2 * H])
@@ -475,16 +477,27 @@ class Engine:
         return site.upT, site.downT
 
     # ------------------------------------------------------------------ public entry
-    def run(self, input_ids, attention_mask, video, video_mask, labels, mlm, want_hidden, logit_rows=None, want_attn=False):
+    def run(self, input_ids, attention_mask, video, video_mask, labels, mlm, want_hidden, logit_rows=None, want_attn=False,
+            inputs_embeds=None):
+        """inputs_embeds: float [B, L, H] in place of E[input_ids] (input_ids is then None; model/deberta.py:1204-1225)."""
         m = self.m
         train = m.training
-        need_grad = torch.is_grad_enabled() and any(self.named[n].requires_grad for n in self.order)
-        if input_ids.device != self.dev:
+        text = input_ids if inputs_embeds is None else inputs_embeds
+        if text.device != self.dev:
             raise RuntimeError(f"inputs must be on {self.dev}")
+        B, Lt = text.shape[:2]
         if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        B, Lt = input_ids.shape
+            attention_mask = (torch.ones_like(input_ids) if inputs_embeds is None
+                              else torch.ones(B, Lt, dtype=torch.long, device=self.dev))
         use_video = bool(self.F) and video is not None
+        # inputs that take a gradient of their own: they become tensor inputs of the step's autograd node (_StepFn)
+        grad_on = torch.is_grad_enabled()
+        grad_in = []
+        if grad_on and use_video and video.requires_grad:
+            grad_in.append(("video", video))
+        if grad_on and inputs_embeds is not None and inputs_embeds.requires_grad:
+            grad_in.append(("embeds", inputs_embeds))
+        need_grad = grad_on and (bool(grad_in) or any(self.named[n].requires_grad for n in self.order))
         T = video.shape[1] if use_video else 0
         S = T + Lt
         if S > self.cfg.max_position_embeddings:
@@ -548,8 +561,13 @@ class Engine:
             run.logit_rows = logit_rows.to(self.dev).to(torch.int32).contiguous().view(-1)
             if pk is not None:
                 run.logit_rows = pk.inv[run.logit_rows.long()].to(torch.int32)
+        run.embeds = inputs_embeds
+        run.video_dtype = video.dtype if use_video else None
+        run.grad_in = tuple(k for k, _ in grad_in)
+        run.hid_grad = bool(want_hidden) and need_grad  # the hidden states handed out are outputs of the step's node
         with L.seed_word(run.seed_word):
-            logits, loss_t = self._forward(run, input_ids.contiguous(), video, use_ans, want_hidden or want_attn)
+            logits, loss_t = self._forward(run, input_ids.contiguous() if inputs_embeds is None else None, video, use_ans,
+                                           want_hidden or want_attn)
         Vout = self.n_ans if use_ans else self.V
         if logit_rows is not None:  # [R, Vout]; under autograd the node below carries them (fine-tuning on the [MASK] rows)
             res = {"logits": logits[:, :Vout], "loss": None, "run": run}
@@ -564,9 +582,13 @@ class Engine:
             # main.py:67-84) and the logits (downstream fine-tuning computes its own loss on them, videoqa.py:66-83,
             # mc.py:64-92)
             lt = loss_t if loss_t is not None else torch.zeros((), dtype=F32, device=self.dev)
-            loss_o, logits_o = _StepFn.apply(self, run, lt, res["logits"], *[self.named[n] for n in self.order])
-            res["logits"] = logits_o
+            hid = res["hidden_states"] if run.hid_grad else ()
+            outs = _StepFn.apply(self, run, lt, res["logits"], len(hid), *hid, *[t for _, t in grad_in],
+                                 *[self.named[n] for n in self.order])
+            loss_o, res["logits"] = outs[:2]
             res["loss"] = loss_o if full_labels is not None else None
+            if hid:
+                res["hidden_states"] = tuple(outs[2:])
         elif full_labels is not None:
             res["loss"] = loss_t
         return res
@@ -800,12 +822,18 @@ class Engine:
         vproj = None
         if T:
             vb = torch.zeros(B * T, self.Fp, dtype=BF16, device=dev)
-            vb[:, : self.F] = video.reshape(B * T, self.F)
+            vb[:, : self.F] = video.detach().reshape(B * T, self.F)  # (detached: its gradient comes from the step's own backward)
             vproj = torch.empty(B * T, H, dtype=F32, device=dev)
             L.gemm(vb, self.Wv, bias=self.P["deberta.embeddings.linear_video.bias"], out_f32=vproj)
             run.video_bf16 = vb
         t0 = torch.empty(B * S, H, dtype=F32, device=dev)
-        L.embed_gather(input_ids, self.E32, vproj, T, t0)
+        if run.embeds is None:
+            L.embed_gather(input_ids, self.E32, vproj, T, t0)
+        else:  # inputs_embeds in place of the gathered table rows (fp32, like them); the video slots in front as the gather puts them
+            g0 = t0.view(B, S, H)
+            if T:
+                g0[:, :T].copy_(vproj.view(B, T, H))
+            g0[:, T:].copy_(run.embeds.detach())
         if pk is not None:
             t0 = t0.index_select(0, pk.sel)
         want_plain = run.p_hid > 0
@@ -826,7 +854,12 @@ class Engine:
         for i in range(nL):
             if i == nL - 1 and self.skip_dead_layer and not want_hidden:
                 break  # its output feeds nothing; executed only when hidden_states are requested
-            if i == nL - 1:
+            if i == nL - 1 and run.hid_grad:
+                # differentiable hidden states: hs[nL] may receive a gradient, so this execution is saved like any other -- a
+                # third execution of the last layer's weights in the backward (LayerSave.extra); it draws the seeds it always drew
+                x = self._layer_fwd(run, i, x, None, Rb)
+                run.layers[-1].extra = True
+            elif i == nL - 1:
                 keep, run.save = run.save, False
                 x = self._layer_fwd(run, i, x, None, Rb)
                 run.save = keep
@@ -1265,7 +1298,9 @@ class Engine:
         # q / k go on the per-step lists, and one chain at the END of backward handles all executions
         # (attn_bwd.pos_table_grads_batched).  ft_ln=False: nothing trainable sits behind the position tables, nothing is kept.
         st = disent_attn_bwd(self, run, sv, dctx, dqkv, None, defer_pos=True)
-        if run.pos_chain is not None:
+        if run.pos_chain is not None and sv.extra:
+            run.pos_extra = (st, sv.seed_pos)  # joins the chain as its LAST execution, where WposT_exec has its weights
+        elif run.pos_chain is not None:
             run.pos_chain.add(st, sv.seed_pos)
         return dqkv
 
@@ -1331,17 +1366,28 @@ class Engine:
         else:
             L.scatter_rows_f32(dqr, rows, dq)  # first contribution: dq is still zero at these rows
 
-    def backward(self, run, gloss: Optional[torch.Tensor], glogits: Optional[torch.Tensor] = None, attach: bool = True):
+    def backward(self, run, gloss: Optional[torch.Tensor], glogits: Optional[torch.Tensor] = None, attach: bool = True,
+                 ghid=None):
         """Explicit backward of _forward; accumulates into the flat gradient buffer (p.grad views).  gloss: gradient
-        of the internal MLM loss (or None); glogits: gradient w.r.t. the returned logits [B,S,Vout] (or None).
+        of the internal MLM loss (or None); glogits: gradient w.r.t. the returned logits [B,S,Vout] (or None); ghid: gradients
+        w.r.t. the returned hidden states, [B,S,H] or None each (run.hid_grad).  Returns the gradients of the inputs named in
+        run.grad_in as a dict ("video": [B,T,F], "embeds": [B,L,H], in the inputs' dtypes).
         attach=False: the caller has already made p.grad the views of the flat buffer (a captured backward must not contain
         the conditional zero fill of attach_grads)."""
         if not run.save:
             raise RuntimeError("forward was run without gradient bookkeeping")
         with L.seed_word(run.seed_word):
-            return self._backward(run, gloss, glogits, attach)
+            return self._backward(run, gloss, glogits, attach, ghid)
 
-    def _backward(self, run, gloss, glogits, attach):
+    def _hid_grad(self, run, ghid, i):
+        """the gradient handed in on hidden_states[i] as fp32 activation rows [N, H], or None"""
+        g = ghid[i] if ghid is not None and i < len(ghid) else None
+        if g is None:
+            return None
+        g = g.reshape(run.B * run.S, self.H).to(F32)
+        return g.index_select(0, run.pk.sel) if run.pk is not None else g.contiguous()
+
+    def _backward(self, run, gloss, glogits, attach, ghid=None):
         cfg, H, dev = self.cfg, self.H, self.dev
         B, S, T = run.B, run.S, run.T
         N = run.N
@@ -1349,7 +1395,9 @@ class Engine:
         if attach:
             self.attach_grads()
         reducer = self.reducer
-        if run.logit_rows is not None and run.logit_rows.numel() == 0 and reducer is None:
+        if ghid is not None and all(g is None for g in ghid):
+            ghid = None
+        if run.logit_rows is not None and run.logit_rows.numel() == 0 and reducer is None and ghid is None:
             return  # no row was asked for: every gradient is exactly zero, nothing is launched (a reducer still needs its buckets)
 
         red = _Ready(self, run, reducer) if reducer is not None else None
@@ -1433,10 +1481,23 @@ class Engine:
             L.gemm(op, WkvT, aux=dx, aux_kind=L.AUX_ADD_F32, out_f32=acc)
             dx = acc
         del dkv_ops
+        # ---- the last layer's own encoder execution (differentiable hidden states only): hs[nL] = layer(hs[nL-1]); a gradient
+        # handed in on hs[nL] flows through it into hs[nL-1] and, as a third execution, into the last layer's parameters
+        if layers and layers[-1].extra:
+            sv = layers.pop()
+            g = self._hid_grad(run, ghid, self.nL)
+            if g is not None:
+                dxe, _ = self._layer_bwd(run, sv, g)
+                dx.add_(dxe)
+                del dxe
+            del sv
         stage_done(f"layer{self.nL - 1}")
         # ---- encoder layers nL-2 .. 0
         while layers:
             sv = layers.pop()
+            g = self._hid_grad(run, ghid, sv.li + 1)  # handed in on this layer's output (behind the convolution for layer 0)
+            if g is not None:
+                dx.add_(g)
             if sv.li == 0 and cfg.conv_kernel_size:
                 dx, dcol = self._conv_bwd(run, dx)
                 dx, _ = self._layer_bwd(run, sv, dx)
@@ -1457,6 +1518,9 @@ class Engine:
             torch.cuda.current_stream().wait_stream(self.side)  # all adapter dW/db are in the flat grad buffer
         # ---- relative-position LayerNorm (receives grads from every layer execution)
         rn = run.rel_norm
+        if run.pos_chain is not None and run.pos_extra is not None:
+            run.pos_chain.add(*run.pos_extra)
+        run.pos_extra = None
         if run.pos_chain is not None:
             dR = pos_table_grads_batched(self, run, run.pos_chain)
             run.pos_chain = None
@@ -1465,6 +1529,9 @@ class Engine:
         if red:
             red.ready("relln")
         # ---- embeddings: dropout -> *mask -> LN ; linear_video
+        g = self._hid_grad(run, ghid, 0)  # hidden_states[0]: the embedding output, behind its dropout
+        if g is not None:
+            dx.add_(g)
         if run.p_hid > 0:
             L.dropout_f32(dx, run.p_hid, run.seed_emb, out_f32=dx)
         en = run.emb_norm
@@ -1488,6 +1555,28 @@ class Engine:
         if red:
             red.ready("emb")
             red.finish()
+        # ---- inputs that take a gradient of their own (run.grad_in): dt0 is the gradient of the embedding rows in front of the
+        # LayerNorm -- the video slots' rows through linear_video, the text rows as they are.  Rows whose mask is 0 are exactly
+        # zero in dt0 (the LayerNorm backward multiplies by the row mask, model/deberta.py:1045-1052), hence in both gradients.
+        gin = {}
+        if "video" in run.grad_in and T:
+            # dvideo = dt0[video rows] . W_video: bf16 operands, fp32 accumulation, against the K-contiguous (transposed) copy of
+            # linear_video.weight, which only a step with this gradient builds
+            wname = "deberta.embeddings.linear_video.weight"
+            WvT = torch.empty(self.F, H, dtype=BF16, device=dev)
+            L.transpose_to_bf16(self.Pb[wname], WvT)
+            dvb = torch.empty(B * T, H, dtype=BF16, device=dev)
+            L.cast_bf16(dv, dvb)
+            dvid = torch.empty(B * T, self.Fp, dtype=F32, device=dev)
+            L.gemm(dvb, WvT, out_f32=dvid, N=self.F)
+            gin["video"] = dvid[:, : self.F].reshape(B, T, self.F).to(run.video_dtype)
+        if "embeds" in run.grad_in:
+            if pk is None:
+                grid = dt0
+            else:  # positions without a row: exactly zero
+                grid = L.zeros(B * S, H, dtype=F32, device=dev).index_copy_(0, pk.sel, dt0)
+            gin["embeds"] = grid.view(B, S, H)[:, T:].to(run.embeds.dtype).contiguous()
+        return gin
 
     def _conv_bwd(self, run, dout):
         """Backward of _conv_fwd: returns (grad of the layer-0 output, grad of the im2col matrix)."""
@@ -1528,6 +1617,7 @@ class _Ready:
 class LayerSave:
     li: int = 0
     emd: bool = False
+    extra: bool = False  # the last encoder layer's own execution (its output is hs[nL] only), saved for differentiable hidden states
     qkv: torch.Tensor = None
     pqk: torch.Tensor = None
     ctx: torch.Tensor = None
@@ -1575,6 +1665,10 @@ class Run:
     seed_word: Optional[torch.Tensor] = None       # device word added to every dropout seed of this pass (see Engine.run)
     pk: Optional["Packing"] = None                 # packed-row layout of this pass (model.packed_rows) or None: the padded [B, S] grid
     N: int = 0                                     # activation rows: B*S, or pk.n
+    embeds: Optional[torch.Tensor] = None          # inputs_embeds [B, L, H] given in place of input_ids
+    grad_in: tuple = ()                            # inputs that take a gradient of their own, as _StepFn lists them: "video", "embeds"
+    hid_grad: bool = False                         # the hidden states handed out are differentiable (outputs of the step's node)
+    video_dtype: Optional[torch.dtype] = None      # the caller's dtype of `video` (its gradient is returned in it)
     _site: int = 0                                 # dropout sites drawn so far (next_seed)
     # ---- forward, before the layers
     mask_i32: torch.Tensor = None                  # [B*S]: the mask as the attention kernels index it (padded grid)
@@ -1622,6 +1716,7 @@ class Run:
     dw_event: Optional[torch.cuda.Event] = None    # ... recorded behind the latest of it (data-parallel buckets wait for it)
     _pos_keep: list = field(default_factory=list)  # captured steps: tensors the side stream reads, referenced for the step's life
     pos_chain: Optional["PosChain"] = None         # attn_bwd.PosChain: what the position-table gradients collect per execution
+    pos_extra: Optional[tuple] = None              # ... of the LayerSave.extra execution, which joins the chain last
 
     def __post_init__(self):
         if not self.N:
@@ -1641,17 +1736,22 @@ class Run:
 class _StepFn(torch.autograd.Function):
     """Single autograd node for the whole model: forward already ran; backward runs Engine.backward which writes the
     gradients straight into the flat grad buffer (p.grad views), so autograd itself accumulates nothing.  logits_t is the
-    [B, S, Vout] grid or, for a `logit_rows` call, the [R, Vout] rows; glogits arrives in the same shape."""
+    [B, S, Vout] grid or, for a `logit_rows` call, the [R, Vout] rows; glogits arrives in the same shape.  `rest` is the
+    n_hid hidden states of an output_hidden_states=True call (outputs of the node too: a gradient handed in on one of them joins
+    the backward where it crosses that boundary), then the inputs that take a gradient of their own (run.grad_in: video,
+    inputs_embeds), then the trainable parameters.  Gradients are not materialised: an output nobody used arrives as None."""
 
     @staticmethod
-    def forward(ctx, engine, run, loss_t, logits_t, *params):
-        ctx.engine, ctx.run = engine, run
+    def forward(ctx, engine, run, loss_t, logits_t, n_hid, *rest):
+        ctx.engine, ctx.run, ctx.n_hid = engine, run, n_hid
         ctx.set_materialize_grads(False)
-        return loss_t.detach().clone(), logits_t.detach()
+        return (loss_t.detach().clone(), logits_t.detach()) + tuple(h.detach() for h in rest[:n_hid])
 
     @staticmethod
-    def backward(ctx, gloss, glogits):
+    def backward(ctx, gloss, glogits, *ghid):
         eng, run = ctx.engine, ctx.run
-        if gloss is not None or glogits is not None:
-            eng.backward(run, gloss, glogits)
-        return (None, None, None, None) + tuple(None for _ in eng.order)
+        gin = {}
+        ghid = ghid if any(g is not None for g in ghid) else None
+        if gloss is not None or glogits is not None or ghid is not None:
+            gin = eng.backward(run, gloss, glogits, ghid=ghid) or {}
+        return (None,) * (5 + ctx.n_hid) + tuple(gin.get(k) for k in run.grad_in) + tuple(None for _ in eng.order)

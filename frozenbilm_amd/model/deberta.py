@@ -467,15 +467,24 @@ class DebertaV2ForMaskedLM(nn.Module):
         prediction head then runs on those rows only and ``logits`` is [len(logit_rows), V] (the downstream loops read one
         [MASK] row per sample: videoqa.py:66-69,164-168, mc.py:166-170).  Under autograd these logits are differentiable and
         the head's backward runs on the same rows; the indices must then be distinct and inside the grid (ValueError), and
-        ``labels`` cannot be given next to them."""
+        ``labels`` cannot be given next to them.  ``inputs_embeds`` (float [B, L, hidden_size]) stands in for ``E[input_ids]``
+        (:1204-1225).  In grad mode a ``video`` or ``inputs_embeds`` that requires grad receives its gradient, and the
+        ``hidden_states`` of an ``output_hidden_states=True`` call are differentiable outputs."""
         if input_ids is not None and inputs_embeds is not None:
             raise ValueError("You cannot specify both input_ids and inputs_embeds at the same time")
-        if input_ids is None:
-            if inputs_embeds is not None:
-                raise NotImplementedError("inputs_embeds is not on the FrozenBiLM hot path")
+        if input_ids is None and inputs_embeds is None:
             raise ValueError("You have to specify either input_ids or inputs_embeds")
+        if inputs_embeds is not None:  # (checked on the host, before the engine is touched)
+            if not torch.is_tensor(inputs_embeds) or inputs_embeds.dim() != 3 or inputs_embeds.shape[-1] != self.config.hidden_size:
+                raise ValueError(f"inputs_embeds must be [batch, text length, hidden_size={self.config.hidden_size}] "
+                                 f"(got {tuple(getattr(inputs_embeds, 'shape', ()))})")
+            if not inputs_embeds.is_floating_point():
+                raise ValueError(f"inputs_embeds must have a floating dtype (got {inputs_embeds.dtype})")
         eng = self.engine()
-        if (self.inference_graphs and not self.packed_rows and not self.decoder_rows and logit_rows is not None and labels is None and not output_hidden_states
+        # The launch-graph routes feed token ids into static buffers and carry no edge to an input: a call with inputs_embeds, or
+        # with a `video` that takes a gradient, runs eagerly (same result as with the graph switches off)
+        eager_only = inputs_embeds is not None or (torch.is_grad_enabled() and video is not None and video.requires_grad)
+        if (not eager_only and self.inference_graphs and not self.packed_rows and not self.decoder_rows and logit_rows is not None and labels is None and not output_hidden_states
                 and not output_attentions and not self.training and not torch.is_grad_enabled()):
             logits = self._graph_forward(eng, input_ids, attention_mask, video, video_mask, mlm, logit_rows)
             if logits is not None:
@@ -487,7 +496,7 @@ class DebertaV2ForMaskedLM(nn.Module):
             from ..train_graph import restore_reducer_overlap
 
             restore_reducer_overlap(eng)  # graphs were on earlier in this run: give the reducer its overlap placement back
-        if (self.training_graphs and not self.packed_rows and not self.decoder_rows and self.training and labels is not None and not output_hidden_states
+        if (not eager_only and self.training_graphs and not self.packed_rows and not self.decoder_rows and self.training and labels is not None and not output_hidden_states
                 and not output_attentions
                 and logit_rows is None and not (self.n_ans and not mlm) and torch.is_grad_enabled()):
             from ..train_graph import graphed_forward
@@ -502,7 +511,7 @@ class DebertaV2ForMaskedLM(nn.Module):
                 out.__dict__["_run"] = run
                 out.__dict__["_fill"] = lambda: eng.fill_logits(run)
                 return out if return_dict is not False else (out["loss"], out["logits"])
-        if (self.finetune_graphs and not self.packed_rows and not self.decoder_rows and self.training and logit_rows is not None
+        if (not eager_only and self.finetune_graphs and not self.packed_rows and not self.decoder_rows and self.training and logit_rows is not None
                 and labels is None and not output_hidden_states and not output_attentions and torch.is_grad_enabled()
                 and logit_rows.numel() > 0):
             from ..train_graph import finetune_forward
@@ -516,7 +525,7 @@ class DebertaV2ForMaskedLM(nn.Module):
         # output_attentions=True (model/deberta.py:1414-1427, :544-560): the fused attention kernel never materialises its
         # probabilities; on request a plain kernel rebuilds them per encoder layer from the stored log-sum-exp (eval mode)
         res = eng.run(input_ids, attention_mask, video, video_mask, labels, mlm, output_hidden_states, logit_rows=logit_rows,
-                      want_attn=bool(output_attentions))
+                      want_attn=bool(output_attentions), inputs_embeds=inputs_embeds)
         out = MaskedLMOutput(loss=res["loss"], logits=res["logits"], hidden_states=res.get("hidden_states"),
                              attentions=res.get("attentions"))
         run = res.get("run")

@@ -364,6 +364,8 @@ def graphed_forward(model, eng, input_ids, attention_mask, video, video_mask, la
     cannot be served from a graph (the caller takes the eager path)."""
     if labels is None or input_ids is None or not torch.is_grad_enabled():
         return None
+    if video is not None and video.requires_grad:
+        return None  # a captured step has no edge to its inputs: the eager path forms the gradient of `video`
     _hold_reducer_after(eng)
     dev = eng.dev
     if attention_mask is None:
@@ -410,6 +412,8 @@ def finetune_forward(model, eng, input_ids, attention_mask, video, video_mask, m
     graph) and the Run, or None when this call cannot be served from a graph (the caller takes the eager path)."""
     import torch.nn.functional as F_
 
+    if input_ids is None or (video is not None and video.requires_grad):
+        return None  # inputs_embeds, or a `video` that takes a gradient: the static feeds hold ids and carry no edge to an input
     _hold_reducer_after(eng)
     cfg = eng.cfg
     use_video = bool(eng.F) and video is not None
