@@ -35,6 +35,7 @@ import torch
 
 from . import lib as L
 from .engine import BF16, F32, Engine, NormRef, Packing, Run, Stream, _ru, _StepFn, check_logit_rows
+from .live_set import LiveSetMixin
 
 
 @dataclass
@@ -102,7 +103,7 @@ def _hid_rows(run, ghid, i):
     return g.index_select(0, run.pk.sel) if run.pk is not None else g.contiguous()
 
 
-class BertEngine:
+class BertEngine(LiveSetMixin):
     # LayerNorm forward / backward and materialisation work on the same representation as the DeBERTa engine's
     _ln = Engine._ln
     _ln_bwd = Engine._ln_bwd
@@ -141,7 +142,8 @@ class BertEngine:
     def _build_flat(self):
         m = self.m
         named = dict(m.named_parameters())
-        order = flat_order(self.nL, [n for n, p in named.items() if p.requires_grad])
+        # the trainable-BY-CONSTRUCTION set (the constructor flags), whatever requires_grad says now: see Engine._build_flat
+        order = flat_order(self.nL, m.trainable_names())
         offs, total = {}, 0
         for n in order:
             offs[n] = total
@@ -166,6 +168,17 @@ class BertEngine:
         self.bucket_ends: Dict[str, int] = {}
         for n in order:
             self.bucket_ends[self._bucket_key(n)] = offs[n] + _ru(named[n].numel(), 8)
+        self._init_live()
+
+    def lowest_layer(self, grad_in=()) -> int:
+        """The lowest encoder layer whose backward a step with the current live set runs: -1 when the embedding stage runs too
+        (linear_video or the embedding LayerNorm is live, or `video` takes a gradient), nL when no layer does."""
+        if grad_in:
+            return -1
+        low = self.nL
+        for n in self.live_order:
+            low = min(low, int(n.split(".")[3]) if n.startswith("bert.encoder.layer.") else -1)
+        return low
 
     @staticmethod
     def _bucket_key(name: str) -> str:
@@ -238,7 +251,8 @@ class BertEngine:
         use_video = bool(self.F) and video is not None
         # a `video` that takes a gradient of its own becomes a tensor input of the step's autograd node (as Engine.run does it)
         grad_in = [("video", video)] if (torch.is_grad_enabled() and use_video and video.requires_grad) else []
-        need_grad = torch.is_grad_enabled() and (bool(grad_in) or any(self.named[n].requires_grad for n in self.order))
+        # the live set (as Engine.run reads it); nothing live and no input with a gradient: no bookkeeping, dropout stays live
+        need_grad = torch.is_grad_enabled() and (self.update_live() or bool(grad_in))
         T = video.shape[1] if use_video else 0
         S = T + Lt
         if S > self.cfg.max_position_embeddings:
@@ -290,6 +304,8 @@ class BertEngine:
             if pk is not None:
                 run.logit_rows = pk.inv[run.logit_rows.long()].to(torch.int32)
         run.grad_in = tuple(k for k, _ in grad_in)
+        if need_grad:  # the backward stops below this layer, and the forward saves nothing below it
+            run.low_layer, run.live_version = self.lowest_layer(run.grad_in), self.live_version
         run.video_dtype = video.dtype if use_video else None
         run.hid_grad = bool(want_hidden) and need_grad  # the hidden states handed out are outputs of the step's node
         with L.seed_word(None):
@@ -335,7 +351,9 @@ class BertEngine:
             pos_rows = self.pos_type.index_select(0, pk.pos)
         emb, _ = self._ln(run, "bert.embeddings.LayerNorm", y=t0, resid=Stream(bf16=None, plain=pos_rows), N=N,
                           want_f32=run.p_hid > 0)
-        run.emb_norm = emb.norm
+        run.emb_norm = emb.norm if run.low_layer < 0 else None
+        if run.low_layer >= 0:
+            run.video_bf16 = None
         if run.p_hid > 0:  # post-LN dropout (:277): the layers see the materialised, dropped-out rows
             run.seed_emb = run.next_seed()
             L.dropout_f32(emb.plain, run.p_hid, run.seed_emb, out_f32=emb.plain, out_bf16=emb.bf16)
@@ -439,13 +457,15 @@ class BertEngine:
         L.gemm(ctx, w["Wo"], bias=w["bo"], out_f32=y1)
         a, seed1 = self._ln(run, p + "attention.output.LayerNorm", y=y1, resid=x, N=N, p_drop=run.p_hid)
         hmid = torch.empty(N, I, dtype=BF16, device=dev)
-        gp = torch.empty(N, I, dtype=BF16, device=dev) if run.save else None
-        L.gemm(a.bf16, w["Wi"], bias=w["bi"], act=L.ACT_GELU_GRAD if run.save else L.ACT_GELU, out_bf16=hmid, out_pre=gp)
+        save = run.save and li >= run.low_layer  # (below the lowest layer with a live leaf nothing is kept for a backward)
+        gp = torch.empty(N, I, dtype=BF16, device=dev) if save else None
+        L.gemm(a.bf16, w["Wi"], bias=w["bi"], act=L.ACT_GELU_GRAD if save else L.ACT_GELU, out_bf16=hmid, out_pre=gp)
         y2 = torch.empty(N, H, dtype=F32, device=dev)
         L.gemm(hmid, w["Wd"], bias=w["bd"], out_f32=y2)
         out, seed2 = self._ln(run, p + "output.LayerNorm", y=y2, resid=a, N=N, p_drop=run.p_hid)
-        run.layers.append(BertLayerSave(qkv=qkv if run.save else None, ctx=ctx if run.save else None, lse=lse, gp=gp,
-                                        ln1=a.norm, ln2=out.norm, seed_att=seed_att, seed_ln1=seed1, seed_ln2=seed2))
+        run.layers.append(BertLayerSave(qkv=qkv if save else None, ctx=ctx if save else None, lse=lse if save else None, gp=gp,
+                                        ln1=a.norm if save else None, ln2=out.norm if save else None, seed_att=seed_att,
+                                        seed_ln1=seed1, seed_ln2=seed2))
         return out
 
     # ------------------------------------------------------------------ backward
@@ -489,7 +509,8 @@ class BertEngine:
             dlog = torch.zeros(N, Vp, dtype=BF16, device=dev)
             dlog[:, :Vout].copy_(gl)
             dx = self._head_bwd(run, None, dlog, dx)
-        for li in reversed(range(self.nL)):
+        low = run.low_layer
+        for li in reversed(range(max(low, 0), self.nL)):
             g = _hid_rows(run, ghid, li + 1)  # handed in on this layer's output
             if g is not None:
                 dx.add_(g)
@@ -497,6 +518,10 @@ class BertEngine:
             if red is not None:
                 red.ready(f"layer{li}")
         run.layers.clear()
+        if low >= 0:  # nothing live below layer `low` and no input takes a gradient: the backward ends here
+            if red is not None:
+                red.finish()  # (the buckets of the stages that did not run leave now, as zeros)
+            return {}
         # ---- embeddings: post-LN dropout, LayerNorm (dgamma / dbeta), linear_video on the video rows
         g = _hid_rows(run, ghid, 0)  # hidden_states[0]: the embedding output, behind its dropout
         if g is not None:
@@ -505,15 +530,17 @@ class BertEngine:
             L.dropout_f32(dx, run.p_hid, run.seed_emb, out_f32=dx)
         dt, dyb = self._ln_bwd("bert.embeddings.LayerNorm", dx, run.emb_norm, 0.0, 0, want_dy_bf16=bool(T))
         want_dvideo = "video" in run.grad_in and T
-        if T and ("bert.embeddings.linear_video.weight" in self.G or want_dvideo):
+        gvw, gvb = (self.Gl.get("bert.embeddings.linear_video." + k) for k in ("weight", "bias"))
+        if T and (gvw is not None or gvb is not None or want_dvideo):
             # the video slots are the first T rows of every sample (packed rows: plen >= T)
             first = torch.arange(B, device=dev, dtype=torch.int32) * S if pk is None else pk.row0[:-1]
             vrows = (first[:, None] + torch.arange(T, device=dev, dtype=torch.int32)[None, :]).view(-1).contiguous()
             dv = torch.empty(B * T, H, dtype=BF16, device=dev)
             L.gather_rows_bf16(dyb, vrows, dv)
-        if T and "bert.embeddings.linear_video.weight" in self.G:
-            L.gemm_tn_acc(dv, run.video_bf16, self.G["bert.embeddings.linear_video.weight"], self.sk_ws, M=H, N=self.F)
-            L.colsum(dv, self.G["bert.embeddings.linear_video.bias"], self._cs_ws)
+        if T and gvw is not None:
+            L.gemm_tn_acc(dv, run.video_bf16, gvw, self.sk_ws, M=H, N=self.F)
+        if T and gvb is not None:
+            L.colsum(dv, gvb, self._cs_ws)
         if red is not None:
             red.ready("emb")
             red.finish()

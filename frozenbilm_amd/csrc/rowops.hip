@@ -2,6 +2,7 @@
 // One wave owns one row (H <= 2048): the row lives in registers, statistics via wave shuffles, 16-byte accesses.
 #include "fbl_common.h"
 #include "../../include/fbl.h"
+#include "../../include/fbl_live.h"
 
 namespace {
 
@@ -763,6 +764,115 @@ __global__ void adam_flat_kernel(float* p, const float* g, float* m, float* v, l
     p[i] = pi - (lr / bc1) * (mi / denom);
   }
 }
+// ---- the same two over a LIVE SET (include/fbl_live.h): sorted, disjoint, 8-aligned ranges of the flat buffers, kept in
+// device memory as tab = {nr, n_live, (begin_0, cum_0), .., (begin_{nr-1}, cum_{nr-1})} with cum_r = the live elements in
+// front of range r.  The kernels walk the COMPACT index space c in [0, n_live) four elements (one 16-byte access) per lane;
+// compact index c lives at begin_r + (c - cum_r) for the last r with cum_r <= c, found by binary search in an LDS copy of
+// the table (a group of four never straddles a range: both ends are multiples of 8).  Nothing outside a range is read into
+// a result or written.
+constexpr int LIVE_MAX_RANGES = 1024;
+struct LiveTab {
+  long begin[LIVE_MAX_RANGES], cum[LIVE_MAX_RANGES];
+};
+__device__ __forceinline__ int live_stage(const int64_t* tab, LiveTab& t, long* n_live) {
+  long nr = tab[0];
+  nr = nr < 0 ? 0 : (nr > LIVE_MAX_RANGES ? LIVE_MAX_RANGES : nr);
+  for (int r = threadIdx.x; r < nr; r += blockDim.x) {
+    t.begin[r] = tab[2 + 2 * r];
+    t.cum[r] = tab[3 + 2 * r];
+  }
+  __syncthreads();
+  *n_live = nr > 0 ? tab[1] : 0;
+  return (int)nr;
+}
+// address of compact index c, or -1 when it would leave the buffer of n elements (a malformed table touches nothing)
+__device__ __forceinline__ long live_addr(const LiveTab& t, int nr, long c, long n) {
+  int lo = 0, hi = nr;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (t.cum[mid] <= c) lo = mid; else hi = mid;
+  }
+  const long a = t.begin[lo] + (c - t.cum[lo]);
+  return (a < 0 || a + 4 > n || (a & 3)) ? -1 : a;
+}
+// One WAVE plays one block of sumsq_kernel: lane l holds the partial sums of that block's threads 4l .. 4l+3 (thread t of
+// virtual block b takes the compact indices b*256 + t + k*nblk*256, in the order of k, as sumsq_kernel does), then the 256
+// partials go through LDS into thread order and through the same wave_sum / four-term sum.  With one range over the whole
+// buffer ws[b] -- and the fold behind it -- carries the bits of fbl_sumsq.
+__global__ __launch_bounds__(256) void sumsq_live_kernel(const float* x, long n, const int64_t* tab, int nblk, float* ws) {
+  __shared__ LiveTab t;
+  __shared__ float part[4][256];
+  long n_live;
+  const int nr = live_stage(tab, t, &n_live);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int vb = blockIdx.x * 4 + w;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (vb < nblk) {
+    // eight 16-byte loads in flight per lane (a wave stands for a whole block: it has to keep that block's bytes moving); the
+    // partial sums still take their elements in the order of k -- a slot past the end adds fma(0, 0, s) = s
+    constexpr int UNR = 8;
+    const long stride = (long)nblk * 256;
+    for (long c = (long)vb * 256 + 4 * lane; c < n_live; c += UNR * stride) {
+      f32x4 xv[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const long cu = c + u * stride;
+        const long a = cu < n_live ? live_addr(t, nr, cu, n) : -1;
+        xv[u] = a >= 0 ? *(const f32x4*)(x + a) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < UNR; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] = __builtin_fmaf(xv[u][e], xv[u][e], s[e]);  // sumsq_kernel's s += x * x is one fma
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) part[w][4 * lane + e] = s[e];
+  __syncthreads();
+  float red[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) red[j] = wave_sum(part[w][64 * j + lane]);
+  if (lane == 0 && vb < nblk) ws[vb] = red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(256) void adam_flat_live_kernel(float* p, const float* g, float* m, float* v, long n,
+                                                             const int64_t* tab, float lr, float b1, float b2, float eps,
+                                                             float wd, float bc1, float bc2, const float* sumsq,
+                                                             float max_norm, float grad_scale) {
+  __shared__ LiveTab t;
+  long n_live;
+  const int nr = live_stage(tab, t, &n_live);
+  float clip = grad_scale;
+  if (sumsq && max_norm > 0.f) {
+    const float norm = sqrtf(sumsq[0]) * grad_scale;
+    clip *= fminf(1.0f, max_norm / (norm + 1e-6f));
+  }
+  for (long c = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; c < n_live; c += (long)gridDim.x * blockDim.x * 4) {
+    const long a = live_addr(t, nr, c, n);
+    if (a < 0) continue;
+    const f32x4 gv = *(const f32x4*)(g + a), pv = *(const f32x4*)(p + a);
+    const f32x4 mv = *(const f32x4*)(m + a), vv = *(const f32x4*)(v + a);
+    f32x4 po, mo, vo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      // adam_flat_kernel's arithmetic, instruction for instruction.  Which products the compiler fuses into an fma depends on
+      // how it vectorises the surrounding code, so here nothing is left to it: contraction is off and the one fma that
+      // adam_flat_kernel's code has (the parameter update) is written out.  tests/test_gpu_adam_live.py holds the two together.
+#pragma clang fp contract(off)
+      float gi = gv[e] * clip;
+      const float pi = pv[e];
+      if (wd != 0.f) gi = gi + wd * pi;
+      const float mi = b1 * mv[e] + (1.f - b1) * gi;
+      const float vi = b2 * vv[e] + ((1.f - b2) * gi) * gi;
+      mo[e] = mi;
+      vo[e] = vi;
+      const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+      po[e] = __builtin_fmaf(-(lr / bc1), mi / denom, pi);
+    }
+    *(f32x4*)(m + a) = mo;
+    *(f32x4*)(v + a) = vo;
+    *(f32x4*)(p + a) = po;
+  }
+}
 __global__ void cast_bf16_kernel(const float* in, bf16* out, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = f2bf(in[i]);
 }
@@ -1095,6 +1205,33 @@ extern "C" int fbl_adam_flat(float* p, const float* g, float* m, float* v, int64
   const float bc2 = 1.0f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adam_flat_kernel, dim3(grid1d(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long)n, lr,
                      beta1, beta2, eps, weight_decay, bc1, bc2, sumsq, max_norm, grad_scale);
+  FBL_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- include/fbl_live.h
+static inline bool live_aligned(const void* a) { return ((uintptr_t)a & 15) == 0; }
+extern "C" int fbl_sumsq_live(const float* x, int64_t n, const int64_t* ranges, float* out_sumsq, float* ws, void* stream) {
+  if (n <= 0) return 0;
+  if (!x || !ranges || !ws || !out_sumsq) return FBL_ERR_ARG;
+  if ((n & 7) || !live_aligned(x)) return FBL_ERR_ALIGN;
+  const int nblk = grid1d(n, 256, SUMSQ_BLOCKS);  // of 256-element virtual blocks, one per wave: fbl_sumsq's count for n elements
+  hipLaunchKernelGGL(sumsq_live_kernel, dim3((nblk + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, (long)n, ranges, nblk, ws);
+  FBL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, nblk, out_sumsq);
+  FBL_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int fbl_adam_flat_live(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* ranges, float lr,
+                                  float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq,
+                                  float max_norm, float grad_scale, void* stream) {
+  if (n <= 0) return 0;
+  if (!p || !g || !m || !v || !ranges) return FBL_ERR_ARG;
+  if ((n & 7) || !live_aligned(p) || !live_aligned(g) || !live_aligned(m) || !live_aligned(v)) return FBL_ERR_ALIGN;
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2 = 1.0f - powf(beta2, (float)step);
+  hipLaunchKernelGGL(adam_flat_live_kernel, dim3(grid1d(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (long)n, ranges, lr, beta1, beta2, eps, weight_decay, bc1, bc2, sumsq, max_norm, grad_scale);
   FBL_CHECK_LAUNCH();
   return 0;
 }

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .live_set import REL_LN, LiveSetMixin, flat_layout, stage_plan
 from .attn_bwd import ATTN_SCALE, _relidx_range, disent_attn_bwd, pos_chain_buffers, pos_table_grads_batched
 from .model.relpos import rel_index_vector
 
@@ -120,7 +121,7 @@ class AdapterSite:
     downT: Optional[torch.Tensor] = None      # after every refresh (_adapter_bwd_operands)
 
 
-class Engine:
+class Engine(LiveSetMixin):
     def __init__(self, model):
         self.m = model
         cfg = model.config
@@ -189,17 +190,17 @@ class Engine:
 
     # ------------------------------------------------------------------ parameter plumbing
     def _build_flat(self):
-        """Re-home every trainable parameter into one flat fp32 buffer (and its grad into a flat grad buffer)."""
+        """Re-home every parameter that is trainable BY CONSTRUCTION (model.trainable_names(): the constructor flags) into one
+        flat fp32 buffer, and its grad into a flat grad buffer.  The layout does not look at `requires_grad`: a parameter the
+        caller froze by hand keeps its place -- offsets, data-parallel buckets and the optimizer-state schema never move during
+        a run; which of them train in a step is the live set (live_set.LiveSetMixin)."""
         from .model.deberta import flat_order
 
         m = self.m
         named = dict(m.named_parameters())
-        train_names = [n for n, p in named.items() if p.requires_grad]
+        train_names = m.trainable_names()
         order = flat_order(self.cfg, train_names)
-        offs, total = {}, 0
-        for n in order:
-            offs[n] = total
-            total += _ru(named[n].numel(), 8)  # keep every view 32-byte aligned
+        offs, total = flat_layout(order, {n: named[n].numel() for n in order})  # every view 32-byte aligned (padded to 8 floats)
         self.flat = torch.zeros(total, dtype=F32, device=self.dev)
         # the gradient buffer is preceded by a few floats that travel with the first data-parallel bucket (the step's logged
         # loss: parallel.GradReducer.stage_scalars); clip + Adam and p.grad only ever see `flat_grad`
@@ -227,6 +228,16 @@ class Engine:
         for n in order:
             key = self._bucket_key(n)
             self.bucket_ends[key] = offs[n] + _ru(named[n].numel(), 8)
+        self._plans: Dict[tuple, object] = {}
+        self._init_live()
+
+    def plan(self, grad_in=()):
+        """the backward stages of a step with the current live set (live_set.stage_plan), per (live set, inputs with a gradient)"""
+        key = (self.live_version, bool(grad_in))
+        pl = self._plans.get(key)
+        if pl is None:
+            pl = self._plans[key] = stage_plan(self.nL, bool(self.cfg.conv_kernel_size), self.live_order, grad_in)
+        return pl
 
     def _bucket_key(self, name: str) -> str:
         if name.startswith("lm_predictions."):
@@ -240,11 +251,12 @@ class Engine:
         return "emb"
 
     def attach_grads(self):
-        """Make p.grad the views of the flat grad buffer; zero it when the user dropped the grads (set_to_none)."""
-        fresh = all(self.named[n].grad is None for n in self.order)
+        """Make p.grad of the LIVE parameters the views of the flat grad buffer; zero it when the user dropped the grads
+        (set_to_none).  A dead parameter gets no .grad (its slice of the buffer is zero: LiveSetMixin._set_live)."""
+        fresh = all(self.named[n].grad is None for n in self.live_order)
         if fresh:
             L.zero_(self.flat_grad)
-        for n in self.order:
+        for n in self.live_order:
             p = self.named[n]
             if p.grad is None:
                 if not fresh:
@@ -497,7 +509,9 @@ class Engine:
             grad_in.append(("video", video))
         if grad_on and inputs_embeds is not None and inputs_embeds.requires_grad:
             grad_in.append(("embeds", inputs_embeds))
-        need_grad = grad_on and (bool(grad_in) or any(self.named[n].requires_grad for n in self.order))
+        # the live set: the trainable-by-construction parameters whose requires_grad is true NOW (a host loop over the flags);
+        # nothing live and no input with a gradient: the call keeps no bookkeeping, as under no_grad (dropout stays live)
+        need_grad = grad_on and (self.update_live() or bool(grad_in))
         T = video.shape[1] if use_video else 0
         S = T + Lt
         if S > self.cfg.max_position_embeddings:
@@ -564,6 +578,8 @@ class Engine:
         run.embeds = inputs_embeds
         run.video_dtype = video.dtype if use_video else None
         run.grad_in = tuple(k for k, _ in grad_in)
+        if need_grad:  # the stages whose backward this step runs: the forward saves nothing below the lowest of them
+            run.plan, run.live_version = self.plan(run.grad_in), self.live_version
         run.hid_grad = bool(want_hidden) and need_grad  # the hidden states handed out are outputs of the step's node
         with L.seed_word(run.seed_word):
             logits, loss_t = self._forward(run, input_ids.contiguous() if inputs_embeds is None else None, video, use_ans,
@@ -797,6 +813,11 @@ class Engine:
             run.layers.append(sv)
         return out
 
+    @staticmethod
+    def _stage_runs(run, stage: str) -> bool:
+        """whether the backward of this step runs `stage` (a Run without a plan -- built by hand -- runs every stage)"""
+        return run.plan is None or run.plan.runs(stage)
+
     def _skip_tail_seeds(self, run, li: int):
         """The seeds of a _layer_tail that is not executed (the decoder with no row selected), drawn in its order -- adapter and
         LayerNorm dropout of the attention output, then of the FFN output: the sites behind it keep their place in the mask stream."""
@@ -854,20 +875,29 @@ class Engine:
         for i in range(nL):
             if i == nL - 1 and self.skip_dead_layer and not want_hidden:
                 break  # its output feeds nothing; executed only when hidden_states are requested
-            if i == nL - 1 and run.hid_grad:
+            # An execution is saved for the backward only when its stage runs there (run.plan): below the lowest stage with a
+            # live leaf nothing is kept -- no LayerSave, no attention probabilities (the forward variant of attn_save_p=False).
+            # The forward itself -- numerics, dropout sites, seeds -- is the same either way.
+            keep = run.save
+            if i == nL - 1:
                 # differentiable hidden states: hs[nL] may receive a gradient, so this execution is saved like any other -- a
-                # third execution of the last layer's weights in the backward (LayerSave.extra); it draws the seeds it always drew
+                # third execution of the last layer's weights in the backward (LayerSave.extra); it draws the seeds it always
+                # drew.  Otherwise its output feeds nothing that has a backward.
+                run.save = keep and run.hid_grad and self._stage_runs(run, "decoder")
                 x = self._layer_fwd(run, i, x, None, Rb)
-                run.layers[-1].extra = True
-            elif i == nL - 1:
-                keep, run.save = run.save, False
-                x = self._layer_fwd(run, i, x, None, Rb)
-                run.save = keep
+                if run.save:
+                    run.layers[-1].extra = True
             else:
+                run.save = keep and self._stage_runs(run, f"layer{i}")
                 x = self._layer_fwd(run, i, x, None, Rb)
+            run.save = keep
             if i == 0 and cfg.conv_kernel_size:
                 x = self._conv_fwd(run, emb, x)
+                if not (run.save and self._stage_runs(run, "conv")):
+                    run.conv_c = run.conv_norm = None
             hs.append(x)
+        if not (run.save and self._stage_runs(run, "emb")):
+            run.emb_norm = run.video_bf16 = None
         # ---- enhanced mask decoder (:1382-1412): q0 = pos_emb + hs[-2]; two passes of the last layer
         kv = hs[nL - 1]
         if run.dec_grid is not None:  # model.decoder_rows: q0 and everything behind it on the selected rows only
@@ -885,8 +915,11 @@ class Engine:
             q32.add_(self.pos_emb.index_select(0, pk.pos))
             qfull[:N].copy_(q32)
         q = Stream(bf16=qfull[:N], plain=q32, full=qfull)
+        keep = run.save
+        run.save = keep and self._stage_runs(run, "decoder")
         for _ in range(2):
             q = self._layer_fwd(run, nL - 1, kv, q, Rb)
+        run.save = keep
         if want_hidden:
             if pk is None:
                 run.hidden_out = tuple(self._materialize(s).view(B, S, H) for s in hs)
@@ -999,6 +1032,8 @@ class Engine:
             q = Stream(bf16=qc32.to(BF16), plain=qc32)
             kvp = torch.empty(N, 2 * H, dtype=BF16, device=dev)
             L.gemm(kv.bf16, W["Wqkv"][H:], bias=W["bqkv"][H:], out_bf16=kvp)
+        keep = run.save
+        run.save = keep and self._stage_runs(run, "decoder")  # (below the lowest live stage: nothing of the passes is kept)
         for _ in range(2):
             sv = LayerSave(li=li, emd=True)
             if run.p_hid > 0:
@@ -1027,6 +1062,7 @@ class Engine:
             if run.save:
                 sv.qc, sv.kvp, sv.pqk, sv.ctx, sv.lse = qp, kvp, pqk, ctx, lse
             q = self._layer_tail(run, li, sv, ctx, q, R)
+        run.save = keep
         # ---- head on the compact rows directly (no gather)
         Vout, table, bias, ldv = self._head_tables(run, use_ans)
         hin = q.bf16 if R else torch.empty(0, H, dtype=BF16, device=dev)
@@ -1128,7 +1164,7 @@ class Engine:
             dt_full[N:].zero_()
         dyb = dy_out if dy_out is not None else (torch.empty(N, H, dtype=BF16, device=self.dev) if want_dy_bf16 else None)
         L.ln_bwd(dout, norm.t, norm.stats, norm.gamma, rowmask=norm.rowmask, p_drop=p_drop, seed=seed, out_dt=dt,
-                 out_dy_bf16=dyb, dgamma=self.G.get(name + ".weight"), dbeta=self.G.get(name + ".bias"), dysum=dysum,
+                 out_dy_bf16=dyb, dgamma=self.Gl.get(name + ".weight"), dbeta=self.Gl.get(name + ".bias"), dysum=dysum,
                  ws=self._ln_ws)
         if tail:
             return dt, dyb, dt_full
@@ -1154,6 +1190,10 @@ class Engine:
             L.gemm(dz, downT, aux=dyb, aux_kind=L.AUX_ADD_BF16, out_bf16=dx)
         sk = max(2, min(16, N // 512))
         nm = site.name
+        # the weight-gradient products of this adapter that feed a LIVE leaf (a dead one gets none: nothing is launched for it)
+        gwu, gwd, gbd = (self.Gl.get(nm + k) for k in (".up.weight", ".down.weight", ".down.bias"))
+        if gwu is None and gwd is None and gbd is None:
+            return dx
 
         if site.grouped:
             # dWu += dy^T z, dWd += dz^T x, dbd += colsum(dz) are NOT launched here: one adapter alone has 48 output tiles.
@@ -1169,9 +1209,12 @@ class Engine:
         # backward reads the weight gradients) with its own workspaces
         self.side.wait_stream(torch.cuda.current_stream())  # inputs (dyb, z, dz, xin_b) are ready once main reaches this point
         with torch.cuda.stream(self.side):
-            L.gemm_tn_acc(dyb, z, self.G[nm + ".up.weight"], self.side_ws, N=A, splitk=sk)      # dWu[H,A] += dy^T z
-            L.gemm_tn_acc(dz, xin_b, self.G[nm + ".down.weight"], self.side_ws, M=A, splitk=sk)  # dWd[A,H] += dz^T x
-            L.colsum(dz, self.G[nm + ".down.bias"], self.side_cs_ws, cols=A)
+            if gwu is not None:
+                L.gemm_tn_acc(dyb, z, gwu, self.side_ws, N=A, splitk=sk)      # dWu[H,A] += dy^T z
+            if gwd is not None:
+                L.gemm_tn_acc(dz, xin_b, gwd, self.side_ws, M=A, splitk=sk)  # dWd[A,H] += dz^T x
+            if gbd is not None:
+                L.colsum(dz, gbd, self.side_cs_ws, cols=A)
         if not torch.cuda.is_current_stream_capturing():
             for t in (dyb, z, dz, xin_b):
                 t.record_stream(self.side)  # keep the allocator from recycling them before the side stream is done
@@ -1200,8 +1243,10 @@ class Engine:
                     names.add(nm)
                     take.setdefault((A, getattr(seg[0], "shape", (None,))[0]), []).append((nm, seg))  # one launch takes one row count
             for (A, _rows), recs in take.items():
-                L.adapter_bwd_dw([([seg], self.G[nm + ".up.weight"], self.G[nm + ".down.weight"], self.G[nm + ".down.bias"])
-                                  for nm, seg in recs], A=A)
+                Gl = getattr(self, "Gl", None)  # the gradient views of the live leaves (before a live set exists: all of them)
+                Gl = self.G if Gl is None else Gl
+                L.adapter_bwd_dw([([seg], Gl.get(nm + ".up.weight"), Gl.get(nm + ".down.weight"), Gl.get(nm + ".down.bias"))
+                                  for nm, seg in recs], A=A)  # (a dead member of a live adapter: no output)
             kept = {id(r) for r in rest}
             for rec in pend:  # [dy | dz | 0] operands whose last reader has now been enqueued go back to the pool (same stream)
                 if id(rec) not in kept and rec[4] is not None and tuple(rec[4].shape) == self._dyz_shape:
@@ -1227,7 +1272,7 @@ class Engine:
         N = dout.shape[0]
         p = f"deberta.encoder.layer.{li}"
         dt2, dy2 = self._ln_bwd(p + ".output.LayerNorm", dout, sv.ln2, run.p_hid, sv.seed_ln2,
-                                dysum=self.G[a2.name + ".up.bias"] if a2 is not None else None)
+                                dysum=self.Gl.get(a2.name + ".up.bias") if a2 is not None else None)
         df = dy2
         if a2 is not None:
             df = self._adapter_bwd(run, a2, dy2, sv.z2, sv.fb, sv.seed_ad2)
@@ -1261,12 +1306,15 @@ class Engine:
                 if Kf > H + A1:
                     dyz[:, H + A1:].zero_()  # finite values under the zero weight columns
             dt1, dy1 = self._ln_bwd(p + ".attention.output.LayerNorm", da, sv.ln1, run.p_hid, sv.seed_ln1,
-                                    dysum=self.G[a1.name + ".up.bias"], dy_out=dyz[:, :H])
+                                    dysum=self.Gl.get(a1.name + ".up.bias"), dy_out=dyz[:, :H])
             self._adapter_bwd(run, a1, dy1, sv.z1, sv.ob, sv.seed_ad1, dz_out=dyz[:, H:H + A1], pooled=pooled)
             L.gemm(dyz, a1.WF, out_bf16=dctx)
+            if pooled is not None and not any((a1.name + k) in self.Gl for k in (".up.weight", ".down.weight", ".down.bias")):
+                # nothing was parked for a dead adapter: this GEMM was the last reader, the buffer returns to the pool at once
+                self._dyz_pool.setdefault(self._dyz_shape, []).append(pooled)
         else:
             dt1, dy1 = self._ln_bwd(p + ".attention.output.LayerNorm", da, sv.ln1, run.p_hid, sv.seed_ln1,
-                                    dysum=self.G[a1.name + ".up.bias"] if a1 is not None else None)
+                                    dysum=self.Gl.get(a1.name + ".up.bias") if a1 is not None else None)
             do = dy1
             if a1 is not None:
                 do = self._adapter_bwd(run, a1, dy1, sv.z1, sv.ob, sv.seed_ad1)
@@ -1392,9 +1440,13 @@ class Engine:
         B, S, T = run.B, run.S, run.T
         N = run.N
         pk = run.pk
+        if run.plan is not None and run.live_version != self.live_version:
+            raise RuntimeError("requires_grad of a trainable parameter changed between this step's forward and its backward: "
+                               "the forward saved what the live set of ITS time needs; change the flags between steps")
         if attach:
             self.attach_grads()
         reducer = self.reducer
+        runs = lambda stage: self._stage_runs(run, stage)  # (run.plan: stages below the lowest live leaf have no backward)
         if ghid is not None and all(g is None for g in ghid):
             ghid = None
         if run.logit_rows is not None and run.logit_rows.numel() == 0 and reducer is None and ghid is None:
@@ -1449,9 +1501,22 @@ class Engine:
             run.dw_ready_keys.append(key)
             self._dw_flush(run, red)
 
+        def end(dx_emb=None):
+            """the tail every backward ends with, wherever its lowest stage is: the parked products, the side stream, the
+            position-table chain (all of its executions have run whenever its LayerNorm is live), the embedding stage when it
+            runs, and the gradient exchange -- finish() releases the buckets of the stages that did not run"""
+            self._dw_flush(run, red, force=True)
+            if run.side_used:
+                torch.cuda.current_stream().wait_stream(self.side)  # all adapter dW/db are in the flat grad buffer
+            return self._backward_bottom(run, red, ghid, dx_emb)
+
         stage_done("head")
         run.pos_chain = None
-        if "deberta.encoder.LayerNorm.weight" in self.G:
+        if not runs("decoder"):
+            return end()
+        # the position-table gradients feed only encoder.LayerNorm: dead, the whole chain (fbl_attn_pos_grad, the strided-batch
+        # projection behind it) is not launched and the attention backward keeps nothing for it
+        if any(REL_LN + k in self.Gl for k in ("weight", "bias")):
             run.pos_chain = pos_chain_buffers(self, run)
             if dec is not None:  # the two decoder executions are the first of the chain also when nothing was selected (R = 0:
                 # they were not saved; zero tables keep the chain's order equal to the order of WposT_exec)
@@ -1474,12 +1539,16 @@ class Engine:
                 L.scatter_rows_f32(dqc, dec.krows.to(torch.int32), dq)
         # q0 = pos_emb + hs[-2]: the query-stream gradient flows into hs[-2] too, next to both passes' key/value-stream
         # gradients [dK | dV] . [Wk ; Wv] -- accumulated by the epilogues of those two GEMMs
-        WkvT = self.Lw[self.nL - 1]["WqkvT"][:, H:]
-        dx = dq
-        for op in dkv_ops:
-            acc = torch.empty(N, H, dtype=F32, device=dev)
-            L.gemm(op, WkvT, aux=dx, aux_kind=L.AUX_ADD_F32, out_f32=acc)
-            dx = acc
+        # (the decoder is the lowest stage that runs: nothing below asks for the gradient of hs[-2], it is not formed)
+        below = run.plan is None or run.plan.lowest < run.plan.stages.index("decoder")
+        dx = None
+        if below:
+            WkvT = self.Lw[self.nL - 1]["WqkvT"][:, H:]
+            dx = dq
+            for op in dkv_ops:
+                acc = torch.empty(N, H, dtype=F32, device=dev)
+                L.gemm(op, WkvT, aux=dx, aux_kind=L.AUX_ADD_F32, out_f32=acc)
+                dx = acc
         del dkv_ops
         # ---- the last layer's own encoder execution (differentiable hidden states only): hs[nL] = layer(hs[nL-1]); a gradient
         # handed in on hs[nL] flows through it into hs[nL-1] and, as a third execution, into the last layer's parameters
@@ -1488,10 +1557,13 @@ class Engine:
             g = self._hid_grad(run, ghid, self.nL)
             if g is not None:
                 dxe, _ = self._layer_bwd(run, sv, g)
-                dx.add_(dxe)
+                if dx is not None:
+                    dx.add_(dxe)
                 del dxe
             del sv
         stage_done(f"layer{self.nL - 1}")
+        if not below:
+            return end()
         # ---- encoder layers nL-2 .. 0
         while layers:
             sv = layers.pop()
@@ -1513,9 +1585,23 @@ class Engine:
             else:
                 dx, _ = self._layer_bwd(run, sv, dx)
             stage_done(f"layer{sv.li}")
-        self._dw_flush(run, red, force=True)
-        if run.side_used:
-            torch.cuda.current_stream().wait_stream(self.side)  # all adapter dW/db are in the flat grad buffer
+        if cfg.conv_kernel_size and runs("conv") and not runs("layer0"):
+            # the conv stage is the lowest that runs (layer 0 was not saved): only its LayerNorm's gamma / beta are wanted
+            g = self._hid_grad(run, ghid, 1)
+            if g is not None:
+                dx.add_(g)
+            cn = run.conv_norm
+            L.ln_bwd(dx, cn.t, cn.stats, cn.gamma, rowmask=cn.rowmask, dgamma=self.Gl.get("deberta.encoder.conv.LayerNorm.weight"),
+                     dbeta=self.Gl.get("deberta.encoder.conv.LayerNorm.bias"), ws=self._ln_ws)
+            stage_done("conv")
+        return end(dx if runs("emb") else None)
+
+    def _backward_bottom(self, run, red, ghid, dx):
+        """The end of every backward: encoder.LayerNorm from the position-table chain (if it is live), the embedding stage
+        (dx: the gradient of the embedding output, or None when that stage does not run), the end of the gradient exchange.
+        Returns the gradients of the inputs named in run.grad_in."""
+        H, dev = self.H, self.dev
+        B, S, T, N, pk = run.B, run.S, run.T, run.N, run.pk
         # ---- relative-position LayerNorm (receives grads from every layer execution)
         rn = run.rel_norm
         if run.pos_chain is not None and run.pos_extra is not None:
@@ -1524,10 +1610,14 @@ class Engine:
         if run.pos_chain is not None:
             dR = pos_table_grads_batched(self, run, run.pos_chain)
             run.pos_chain = None
-            L.ln_bwd(dR, rn.t, rn.stats, rn.gamma, dgamma=self.G.get("deberta.encoder.LayerNorm.weight"),
-                     dbeta=self.G.get("deberta.encoder.LayerNorm.bias"), ws=self._ln_ws)
+            L.ln_bwd(dR, rn.t, rn.stats, rn.gamma, dgamma=self.Gl.get("deberta.encoder.LayerNorm.weight"),
+                     dbeta=self.Gl.get("deberta.encoder.LayerNorm.bias"), ws=self._ln_ws)
         if red:
             red.ready("relln")
+        if dx is None:  # nothing live in the embedding stage and no input takes a gradient: the backward ends here
+            if red:
+                red.finish()  # (the buckets of the stages that did not run leave now, as zeros)
+            return {}
         # ---- embeddings: dropout -> *mask -> LN ; linear_video
         g = self._hid_grad(run, ghid, 0)  # hidden_states[0]: the embedding output, behind its dropout
         if g is not None:
@@ -1537,21 +1627,23 @@ class Engine:
         en = run.emb_norm
         dt0 = torch.empty(N, H, dtype=F32, device=dev)
         L.ln_bwd(dx, en.t, en.stats, en.gamma, rowmask=en.rowmask, out_dt=dt0,
-                 dgamma=self.G.get("deberta.embeddings.LayerNorm.weight"), dbeta=self.G.get("deberta.embeddings.LayerNorm.bias"),
+                 dgamma=self.Gl.get("deberta.embeddings.LayerNorm.weight"), dbeta=self.Gl.get("deberta.embeddings.LayerNorm.bias"),
                  ws=self._ln_ws)
-        if T:
+        gvw, gvb = (self.Gl.get("deberta.embeddings.linear_video." + k) for k in ("weight", "bias"))
+        if T and (gvw is not None or gvb is not None or "video" in run.grad_in):
             if pk is None:
                 dv = dt0.view(B, S, H)[:, :T].reshape(B * T, H).contiguous()
             else:  # the video slots are the first T rows of every sample
                 dv = dt0.index_select(0, (pk.row0[:-1].long()[:, None] + torch.arange(T, device=dev)[None]).reshape(-1))
-            Kp = _ru(B * T, 64)
-            dvT = torch.empty(H, Kp, dtype=BF16, device=dev)
-            vT = torch.empty(self.Fp, Kp, dtype=BF16, device=dev)
-            L.transpose_to_bf16(dv, dvT)
-            L.transpose_to_bf16(run.video_bf16, vT)
-            L.gemm(dvT, vT, aux=self.G["deberta.embeddings.linear_video.weight"], aux_kind=L.AUX_ADD_F32,
-                   out_f32=self.G["deberta.embeddings.linear_video.weight"], N=self.F)
-            L.colsum(dv, self.G["deberta.embeddings.linear_video.bias"], self._cs_ws)
+            if gvw is not None:  # (dead: its weight-gradient product is not formed)
+                Kp = _ru(B * T, 64)
+                dvT = torch.empty(H, Kp, dtype=BF16, device=dev)
+                vT = torch.empty(self.Fp, Kp, dtype=BF16, device=dev)
+                L.transpose_to_bf16(dv, dvT)
+                L.transpose_to_bf16(run.video_bf16, vT)
+                L.gemm(dvT, vT, aux=gvw, aux_kind=L.AUX_ADD_F32, out_f32=gvw, N=self.F)
+            if gvb is not None:
+                L.colsum(dv, gvb, self._cs_ws)
         if red:
             red.ready("emb")
             red.finish()
@@ -1585,8 +1677,8 @@ class Engine:
         cn = run.conv_norm
         dt = torch.empty(N, H, dtype=F32, device=dev)
         L.ln_bwd(dout, cn.t, cn.stats, cn.gamma, rowmask=cn.rowmask, out_dt=dt,
-                 dgamma=self.G.get("deberta.encoder.conv.LayerNorm.weight"),
-                 dbeta=self.G.get("deberta.encoder.conv.LayerNorm.bias"), ws=self._ln_ws)
+                 dgamma=self.Gl.get("deberta.encoder.conv.LayerNorm.weight"),
+                 dbeta=self.Gl.get("deberta.encoder.conv.LayerNorm.bias"), ws=self._ln_ws)
         dc = torch.empty(N, H, dtype=BF16, device=dev)
         L.dropout_gelu_bwd(dt, run.conv_c, run.p_hid, run.seed_conv, out_bf16=dc)
         dcol = torch.empty(N, 3 * H, dtype=F32, device=dev)
@@ -1717,6 +1809,10 @@ class Run:
     _pos_keep: list = field(default_factory=list)  # captured steps: tensors the side stream reads, referenced for the step's life
     pos_chain: Optional["PosChain"] = None         # attn_bwd.PosChain: what the position-table gradients collect per execution
     pos_extra: Optional[tuple] = None              # ... of the LayerSave.extra execution, which joins the chain last
+    # ---- partial fine-tuning
+    plan: Optional[object] = None                  # live_set.StagePlan: the stages whose backward runs (None: all of them)
+    live_version: int = 0                          # the engine's live set this step was planned for
+    low_layer: int = -1                            # BertEngine: the lowest layer whose backward runs (-1: the embeddings too)
 
     def __post_init__(self):
         if not self.N:

@@ -63,6 +63,7 @@ def _header_signatures(header: str) -> dict:
 SIGNATURES = _header_signatures("fbl.h")
 MHA_SIGNATURES = _header_signatures("fbl_mha.h")      # the BERT variant's fused attention
 QROWS_SIGNATURES = _header_signatures("fbl_qrows.h")  # the enhanced mask decoder's attention on selected query rows
+LIVE_SIGNATURES = _header_signatures("fbl_live.h")    # clip norm and Adam over a live set of the flat trainable buffer
 
 _LIB = None
 
@@ -78,7 +79,8 @@ def load(path: Optional[str] = None):
             f"{p} not found: the FrozenBiLM MI355X path needs its HIP library (python -m frozenbilm_amd.build); "
             "there is no CPU/eager fallback")
     lib = C.CDLL(p)
-    for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
+                              *LIVE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -741,6 +743,38 @@ def adam_flat(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, sumsq_t=Non
     _chk(load().fbl_adam_flat(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                               float(weight_decay), int(step), _p(sumsq_t), float(max_norm), float(grad_scale),
                               _stream()), "fbl_adam_flat")
+
+
+LIVE_MAX_RANGES = 1024  # ranges fbl_sumsq_live / fbl_adam_flat_live look at (include/fbl_live.h)
+
+
+def live_table(ranges, n: int, device) -> torch.Tensor:
+    """The device table of include/fbl_live.h for `ranges` = [(begin, end), ..] inside a flat buffer of n elements; refuses
+    anything but sorted, disjoint, non-empty, 8-aligned ranges (the kernels trust the table they are given)."""
+    if len(ranges) > LIVE_MAX_RANGES:
+        raise ValueError(f"{len(ranges)} live ranges: the kernels take {LIVE_MAX_RANGES}")
+    tab, cum, last = [len(ranges), 0], 0, 0
+    for b, e in ranges:
+        if b < last or e <= b or e > n or b % 8 or e % 8:
+            raise ValueError(f"live range [{b}, {e}) of {n}: ranges must be sorted, disjoint, non-empty and 8-aligned")
+        tab += [b, cum]
+        cum += e - b
+        last = e
+    tab[1] = cum
+    return torch.tensor(tab, dtype=torch.int64, device=device)
+
+
+def sumsq_live(x, table, out, ws):
+    """out[0] += sum x^2 over the live ranges of `table` (live_table)"""
+    _req(x, torch.float32, "x"); _req(table, torch.int64, "table")
+    _chk(load().fbl_sumsq_live(_p(x), x.numel(), _p(table), _p(out), _p(ws), _stream()), "fbl_sumsq_live")
+
+
+def adam_flat_live(p, g, m, v, table, lr, beta1, beta2, eps, weight_decay, step, sumsq_t=None, max_norm=0.0, grad_scale=1.0):
+    _req(table, torch.int64, "table")
+    _chk(load().fbl_adam_flat_live(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(table), float(lr), float(beta1), float(beta2),
+                                   float(eps), float(weight_decay), int(step), _p(sumsq_t), float(max_norm), float(grad_scale),
+                                   _stream()), "fbl_adam_flat_live")
 
 
 def cast_bf16(x, out):

@@ -141,6 +141,7 @@ class BertForMaskedLM(nn.Module):
         return bool(self.ft_ln and name.startswith("bert.") and "LayerNorm" in name)
 
     # module tree, engine life cycle and dropout seeds work as on the DeBERTa model
+    trainable_names = DebertaV2ForMaskedLM.trainable_names
     _module = DebertaV2ForMaskedLM._module
     _register = DebertaV2ForMaskedLM._register
     get_param = DebertaV2ForMaskedLM.get_param

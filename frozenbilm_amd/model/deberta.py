@@ -265,6 +265,14 @@ class DebertaV2ForMaskedLM(nn.Module):
             return True
         return bool(self.ft_ln and "LayerNorm" in name)
 
+    def trainable_names(self) -> List[str]:
+        """The trainable-BY-CONSTRUCTION set, in `named_parameters()` order: what the constructor flags make trainable, whatever
+        `requires_grad` says right now.  The engine lays its flat buffer out by it and the optimizer numbers its states by it,
+        so neither moves when the caller freezes or unfreezes a parameter during a run; which of these train in a step is the
+        live set (frozenbilm_amd/live_set.py).  A parameter outside this set that asks for a gradient is refused by the next
+        grad-mode forward (live_set.unsupported_leaf_message)."""
+        return [n for n, _ in self.named_parameters() if self._trainable(n)]
+
     # ---------------------------------------------------------------- reference API
     @property
     def device(self):

@@ -49,7 +49,7 @@ from .engine import Run, check_logit_rows
 
 F32 = torch.float32
 ROW_BUCKET = 256  # capacity granularity of the labelled-row list
-MAX_GRAPHS = 4    # captured (batch shape, row capacity) configurations kept per model (each owns one step's activations)
+MAX_GRAPHS = 4    # captured (batch shape, row capacity, live set) configurations kept per model (each owns one step's activations)
 MAX_CAPTURES = 12  # captures per model before the feature switches itself off with a warning (a shape-static loop needs 1-3)
 
 
@@ -109,6 +109,9 @@ class _GraphedPair:
         run = Run(B=B, S=T + Lt, T=T, Lt=Lt, train=True, save=True, seed_base=0, p_hid=cfg.hidden_dropout_prob,
                   p_att=cfg.attention_probs_dropout_prob, p_ad=m.adapter_dropout)
         run.seed_word = self.seed_word
+        # the stages this capture saves for and back-propagates through: those of the live set it was captured under (the live
+        # set's version is part of the cache key, so another set gets a capture of its own)
+        run.plan, run.live_version = eng.plan(()), eng.live_version
         am = st["attention_mask"]
         if T:
             vm = st.get("video_mask")
@@ -156,7 +159,7 @@ class _GraphedPair:
     def _replay_backward(self):
         eng = self.eng
         named, G = eng.named, eng.G
-        if not all(named[n].grad is not None and named[n].grad.data_ptr() == G[n].data_ptr() for n in eng.order):
+        if not all(named[n].grad is not None and named[n].grad.data_ptr() == G[n].data_ptr() for n in eng.live_order):
             eng.attach_grads()  # (skipped while every p.grad still is its view of the flat buffer -- zero_grad(set_to_none=True)
             #                      or a foreign / dropped .grad on ANY parameter brings the full pass back; ~300 pointer compares)
         self.g_bwd.replay()
@@ -366,6 +369,8 @@ def graphed_forward(model, eng, input_ids, attention_mask, video, video_mask, la
         return None
     if video is not None and video.requires_grad:
         return None  # a captured step has no edge to its inputs: the eager path forms the gradient of `video`
+    if not eng.update_live():
+        return None  # nothing is live: the eager path runs the call without gradient bookkeeping
     _hold_reducer_after(eng)
     dev = eng.dev
     if attention_mask is None:
@@ -392,7 +397,7 @@ def graphed_forward(model, eng, input_ids, attention_mask, video, video_mask, la
     if r_cap > R:  # pad with the first unlabelled row (found on the device: no second synchronisation; R < N: one exists)
         free = torch.argmax((flat == -100).to(torch.int8)).view(1)
         rows = torch.cat([rows, free.expand(r_cap - R)])
-    key = (id(eng), B, Lt, T, "video_mask" in feed, r_cap, _dtypes(feed))
+    key = (id(eng), B, Lt, T, "video_mask" in feed, r_cap, _dtypes(feed), eng.live_version)
 
     def warm_up():
         eng.run(feed["input_ids"], feed["attention_mask"], feed.get("video"), feed.get("video_mask"), feed["labels"],
@@ -414,6 +419,8 @@ def finetune_forward(model, eng, input_ids, attention_mask, video, video_mask, m
 
     if input_ids is None or (video is not None and video.requires_grad):
         return None  # inputs_embeds, or a `video` that takes a gradient: the static feeds hold ids and carry no edge to an input
+    if not eng.update_live():
+        return None  # nothing is live: the eager path runs the call without gradient bookkeeping
     _hold_reducer_after(eng)
     cfg = eng.cfg
     use_video = bool(eng.F) and video is not None
@@ -439,7 +446,7 @@ def finetune_forward(model, eng, input_ids, attention_mask, video, video_mask, m
         if video_mask is not None:
             feed["video_mask"] = video_mask.contiguous()
     use_ans = bool(model.n_ans) and not mlm
-    key = (id(eng), B, Lp, T, "video_mask" in feed, rows.numel(), bool(mlm), _dtypes(feed))
+    key = (id(eng), B, Lp, T, "video_mask" in feed, rows.numel(), bool(mlm), _dtypes(feed), eng.live_version)
 
     def warm_up():
         lg = eng.run(feed["input_ids"], feed["attention_mask"], feed.get("video"), feed.get("video_mask"), None, mlm, False,

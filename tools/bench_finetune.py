@@ -108,6 +108,18 @@ def host_issue_stats(legs, n):
     return {k: band(v) for k, v in issue.items()}
 
 
+def peak_memory(legs):
+    """per leg torch.cuda.max_memory_allocated of one step, in MB (a pass of its own, after the timed ones)"""
+    out = {}
+    for k, f in legs.items():
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        f()
+        torch.cuda.synchronize()
+        out[k] = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+    return out
+
+
 def workload(name):
     cfg = DebertaV2Config()
     if a.layers:
@@ -144,7 +156,25 @@ def workload(name):
     feed = dict(video=video, video_mask=vmask, input_ids=ids.to(dev), attention_mask=(ids != 0).long().to(dev))
     rows_packed = int((tlen + T).sum())  # every sample keeps its video slots and its text up to the last token
 
-    def step(**opt_in):
+    names = m.trainable_names()
+    named = dict(m.named_parameters())
+    nL = cfg.num_hidden_layers
+
+    def set_live(kind):
+        """partial fine-tuning legs: None = everything live; "topK" = adapters and LayerNorms of the top K layers (the head's
+        LayerNorm with them), linear_video and everything below dead; "no_relln" = everything but deberta.encoder.LayerNorm"""
+        for n in names:
+            if kind is None:
+                on = True
+            elif kind == "no_relln":
+                on = not n.startswith("deberta.encoder.LayerNorm.")
+            else:
+                k = int(kind[3:])
+                on = n.startswith("lm_predictions.") or (n.startswith("deberta.encoder.layer.") and int(n.split(".")[3]) >= nL - k)
+            named[n].requires_grad_(on)
+
+    def step(live=None, **opt_in):
+        set_live(live)
         args = types.SimpleNamespace(max_feats=T, use_video=True, **opt_in)
         m.packed_rows = bool(opt_in.get("packed_rows"))
         m.decoder_rows = bool(opt_in.get("decoder_rows"))
@@ -161,12 +191,16 @@ def workload(name):
     legs = {"full": lambda: step(), "rows": lambda: step(train_logit_rows=True), "rows_packed": lambda: step(packed_rows=True),
             "rows_decoder": lambda: step(train_logit_rows=True, decoder_rows=True),
             "rows_packed_decoder": lambda: step(packed_rows=True, decoder_rows=True),
-            "rows_graphs": lambda: step(finetune_graphs=True)}
+            "rows_graphs": lambda: step(finetune_graphs=True),
+            # partial fine-tuning (the default route, flags toggled): the backward stops below the lowest live layer
+            "live_top24": lambda: step(live="top24"), "live_top12": lambda: step(live="top12"), "live_top4": lambda: step(live="top4"),
+            "live_no_relln": lambda: step(live="no_relln")}
     if a.legs:
         legs = {k: legs[k] for k in a.legs.split(",")}
     res = {"shape": dict(samples=n, S=S, T=T, n_ans=n_ans, candidates=C, layers=cfg.num_hidden_layers, mask_rows=n),
            "rows": {"padded": n * S, "packed": rows_packed, "share": round(rows_packed / (n * S), 3)},
            "step_ms": alternate_stats(legs, a.steps, a.warmup), "host_ms": host_issue_stats(legs, a.steps),
+           "peak_mb": peak_memory(legs),
            "graph_captures": m.__dict__.get("_finetune_graph_captures", 0),
            "graph_replays": m.__dict__.get("_finetune_graph_replays", 0)}
     if "full" in legs:
