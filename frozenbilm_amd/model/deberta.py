@@ -224,11 +224,13 @@ class DebertaV2ForMaskedLM(nn.Module):
         emb.register_buffer("position_ids", torch.arange(cfg.max_position_embeddings).expand((1, -1)))
         self._engine = None
         self.engine_options = {}  # read once when the engine is built (engine.Engine.__init__ lists the keys; defaults = shipped)
-        self.inference_graphs = False  # opt-in: replay the `logit_rows` inference forward as one hipGraph (_graph_forward)
-        self.training_graphs = False  # opt-in: the MLM training step as two replayed hipGraphs (train_graph.py)
-        # opt-in: the fine-tuning step (`logit_rows` under autograd, no labels) as two replayed hipGraphs, the text padded to a
-        # length bucket of GRAPH_L_BUCKET; not used while packed_rows / decoder_rows is on (train_graph.finetune_forward)
-        self.finetune_graphs = False
+        # the launch graphs (train_graph.py), each opt-in: the `logit_rows` inference forward replayed as one hipGraph, the MLM
+        # training step as two, the fine-tuning step (`logit_rows` under autograd, no labels) as two; `_graph_routes` is what
+        # the routes remember besides their caches (train_graph.stats)
+        self.inference_graphs = self.training_graphs = self.finetune_graphs = False
+        from ..train_graph import new_states
+
+        self._graph_routes = new_states()
         # opt-in: ragged batches run without the padding rows behind each sample's last used position (engine.Packing) whenever
         # the call's outputs live on selected rows (labels / logit_rows given).  Rows that exist get the same values as on the
         # padded grid; `logits` / `hidden_states` read as zero at the dropped positions (the reference computes values there
@@ -331,9 +333,10 @@ class DebertaV2ForMaskedLM(nn.Module):
     def invalidate(self):
         """Drop the packed bf16 operands / flat buffers (after load_state_dict, .to(), set_answer_embeddings)."""
         self._engine = None
-        self.__dict__.pop("_graph_cache", None)  # captured graphs hold the old engine's buffers
-        self.__dict__.pop("_train_graphs", None)
-        self.__dict__.pop("_finetune_graph_cache", None)
+        from ..train_graph import ROUTES
+
+        for route in ROUTES:  # captured graphs hold the old engine's buffers
+            self.__dict__.pop(route.cache, None)
 
     def _load_from_state_dict(self, *a, **k):
         self.invalidate()
@@ -374,85 +377,7 @@ class DebertaV2ForMaskedLM(nn.Module):
             self._seed_salt = ((torch.initial_seed() & 0xFFFFFFFF) * 2654435761 + rank * 40503 + 12345) & 0xFFFFFFFFFFFF
         return (self.step_seed * 1000003 + self._seed_salt) & 0xFFFFFFFFFFFF
 
-    # ---------------------------------------------------------------- inference launch graphs (opt-in)
-    GRAPH_L_BUCKET = 32  # text lengths are padded up to a multiple of this inside the graph path
-    GRAPH_CACHE = 6      # captured (batch, length, rows) configurations kept per model
-
-    def _graph_forward(self, eng, input_ids, attention_mask, video, video_mask, mlm, logit_rows):
-        """The `logit_rows` inference forward (what `videoqa.evaluate` / `mc.evaluate` run per batch, videoqa.py:157-168,
-        mc.py:160-172) as ONE hipGraph replay: ~700 kernel launches cost the host ~10 ms per batch when issued one by one,
-        more than the loops have to spare next to an 18 ms forward.  The text is padded to the next multiple of
-        GRAPH_L_BUCKET with pad tokens (masked: a sample's logits do not depend on padding), the inputs are copied into
-        the graph's static buffers, the graph -- captured on first use of a (batch, padded length, frames, rows)
-        configuration, least recently used ones dropped -- is replayed and the [rows, V] logits are returned as a copy.
-        Returns None when the configuration cannot be captured (the caller then takes the eager path)."""
-        import torch.nn.functional as F_
-
-        # operands of the trainable weights / composed adapter rows are rebuilt (in place) outside the graph: on every call,
-        # or -- inside weights_frozen(), where the evaluate loops run -- only when something wrote to the parameters
-        eng.prepare_inference()
-        B, Lt = input_ids.shape
-        T = video.shape[1] if (video is not None and eng.F) else 0
-        from ..train_graph import bucket_length, remap_rows
-
-        Lp = bucket_length(Lt, T, self.config.max_position_embeddings, self.GRAPH_L_BUCKET)
-        if Lp is None:
-            return None
-        if attention_mask is None:
-            attention_mask = torch.ones_like(input_ids)
-        rows = remap_rows(logit_rows.to(eng.dev).long().view(-1), T + Lt, T + Lp)
-        key = (id(eng), B, Lp, T, video_mask is not None, rows.numel(), bool(mlm))
-        cache = self.__dict__.setdefault("_graph_cache", {})
-        feed = dict(input_ids=F_.pad(input_ids, (0, Lp - Lt), value=self.config.pad_token_id),
-                    attention_mask=F_.pad(attention_mask, (0, Lp - Lt), value=0), rows=rows.to(torch.int32))
-        if T:
-            feed["video"] = video
-            if video_mask is not None:
-                feed["video_mask"] = video_mask
-        ent = cache.pop(key, None)
-        if ent is None:
-            for k in [k for k in cache if k[0] != id(eng)]:
-                del cache[k]
-            while len(cache) >= self.GRAPH_CACHE:
-                del cache[next(iter(cache))]
-            static = {k: v.to(eng.dev).clone() for k, v in feed.items()}
-
-            def run_once():
-                return eng.run(static["input_ids"], static["attention_mask"], static.get("video"), static.get("video_mask"),
-                               None, mlm, False, logit_rows=static["rows"])["logits"]
-
-            eng._no_pos_cache = True  # the captured forward recomputes the position projections: it reads nothing that a later
-            try:                      # rebuild of the trainable operands would re-allocate behind its back
-                run_once()  # warm-up outside the capture (lazy initialisation, allocator)
-                torch.cuda.synchronize(eng.dev)
-                graph = torch.cuda.CUDAGraph()
-                import gc
-
-                gc_was_on = gc.isenabled()  # (no cyclic collection inside a capture: train_graph.TrainStep.capture)
-                gc.collect()
-                gc.disable()
-                try:
-                    with torch.cuda.graph(graph):
-                        logits = run_once()
-                finally:
-                    if gc_was_on:
-                        gc.enable()
-            except Exception as e:  # noqa: BLE001
-                import warnings
-
-                torch.cuda.synchronize(eng.dev)
-                warnings.warn(f"inference graph capture failed ({type(e).__name__}: {e}); staying on the eager path")
-                self.inference_graphs = False
-                return None
-            finally:
-                eng._no_pos_cache = False
-            ent = (graph, static, logits)
-        graph, static, logits = ent
-        cache[key] = ent  # most recently used last
-        for k, v in feed.items():
-            static[k].copy_(v, non_blocking=True)
-        graph.replay()
-        return logits.clone()
+    GRAPH_L_BUCKET = 32  # the launch graphs pad text lengths up to a multiple of this (train_graph.build_feed)
 
     def forward(
         self,
@@ -489,51 +414,20 @@ class DebertaV2ForMaskedLM(nn.Module):
             if not inputs_embeds.is_floating_point():
                 raise ValueError(f"inputs_embeds must have a floating dtype (got {inputs_embeds.dtype})")
         eng = self.engine()
-        # The launch-graph routes feed token ids into static buffers and carry no edge to an input: a call with inputs_embeds, or
-        # with a `video` that takes a gradient, runs eagerly (same result as with the graph switches off)
-        eager_only = inputs_embeds is not None or (torch.is_grad_enabled() and video is not None and video.requires_grad)
-        if (not eager_only and self.inference_graphs and not self.packed_rows and not self.decoder_rows and logit_rows is not None and labels is None and not output_hidden_states
-                and not output_attentions and not self.training and not torch.is_grad_enabled()):
-            logits = self._graph_forward(eng, input_ids, attention_mask, video, video_mask, mlm, logit_rows)
-            if logits is not None:
-                out = MaskedLMOutput(loss=None, logits=logits, hidden_states=None, attentions=None)
-                return out if return_dict is not False else (logits,)
-        if (not self.training_graphs and not self.finetune_graphs and eng.reducer is not None
-                and "_overlap_before_graphs" in eng.reducer.__dict__ and not self.__dict__.get("_train_graphs_auto_off")
-                and not self.__dict__.get("_finetune_graphs_auto_off")):
-            from ..train_graph import restore_reducer_overlap
+        from .. import train_graph as TG  # (the launch graphs, opt-in: which calls they serve is TG.route_for's to say)
 
-            restore_reducer_overlap(eng)  # graphs were on earlier in this run: give the reducer its overlap placement back
-        if (not eager_only and self.training_graphs and not self.packed_rows and not self.decoder_rows and self.training and labels is not None and not output_hidden_states
-                and not output_attentions
-                and logit_rows is None and not (self.n_ans and not mlm) and torch.is_grad_enabled()):
-            from ..train_graph import graphed_forward
-
-            got = graphed_forward(self, eng, input_ids, attention_mask, video, video_mask, labels)
-            if got is not None:
-                loss, run = got
-                B, S = run.B, run.S
-                # (the logits of a graphed step carry no autograd edge: gradients flow through `.loss`)
-                out = MaskedLMOutput(loss=loss, logits=run.logits.view(B, S, -1)[:, :, : run.Vout], hidden_states=None,
-                                     attentions=None)
-                out.__dict__["_run"] = run
-                out.__dict__["_fill"] = lambda: eng.fill_logits(run)
-                return out if return_dict is not False else (out["loss"], out["logits"])
-        if (not eager_only and self.finetune_graphs and not self.packed_rows and not self.decoder_rows and self.training and logit_rows is not None
-                and labels is None and not output_hidden_states and not output_attentions and torch.is_grad_enabled()
-                and logit_rows.numel() > 0):
-            from ..train_graph import finetune_forward
-
-            got = finetune_forward(self, eng, input_ids, attention_mask, video, video_mask, mlm, logit_rows)
-            if got is not None:
-                logits, run = got
-                out = MaskedLMOutput(loss=None, logits=logits, hidden_states=None, attentions=None)
-                out.__dict__["_run"] = run
-                return out if return_dict is not False else (logits,)
+        TG.restore_reducer_overlap_if_routes_off(self, eng)
+        route = TG.route_for(self, TG.Call(
+            ids=input_ids is not None, embeds=inputs_embeds is not None, labels=labels is not None,
+            rows=None if logit_rows is None else logit_rows.numel(), video_grad=video is not None and video.requires_grad,
+            mlm=bool(mlm), hidden_states=bool(output_hidden_states), attentions=bool(output_attentions),
+            grad=torch.is_grad_enabled()))
+        res = route and TG.serve(self, eng, route, input_ids, attention_mask, video, video_mask, labels, mlm, logit_rows)
         # output_attentions=True (model/deberta.py:1414-1427, :544-560): the fused attention kernel never materialises its
         # probabilities; on request a plain kernel rebuilds them per encoder layer from the stored log-sum-exp (eval mode)
-        res = eng.run(input_ids, attention_mask, video, video_mask, labels, mlm, output_hidden_states, logit_rows=logit_rows,
-                      want_attn=bool(output_attentions), inputs_embeds=inputs_embeds)
+        if res is None:
+            res = eng.run(input_ids, attention_mask, video, video_mask, labels, mlm, output_hidden_states,
+                          logit_rows=logit_rows, want_attn=bool(output_attentions), inputs_embeds=inputs_embeds)
         out = MaskedLMOutput(loss=res["loss"], logits=res["logits"], hidden_states=res.get("hidden_states"),
                              attentions=res.get("attentions"))
         run = res.get("run")

@@ -58,6 +58,7 @@ class GradReducer:
         self.overlap = overlap or "attention_windows"
         if self.overlap not in OVERLAP_MODES:
             raise ValueError(f"overlap must be one of {OVERLAP_MODES}, got {self.overlap!r}")
+        self._overlap_before_graphs = None  # the placement a training launch-graph route took away (train_graph._hold_reducer_after)
         self._set_buckets(bucket_ends)
         self.pending: List = []
         self.launched: List[Tuple[int, int]] = []

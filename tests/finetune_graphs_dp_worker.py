@@ -72,7 +72,7 @@ def main():
     torch.cuda.synchronize()
     grads = {n: p.grad.detach().float().cpu() for n, p in m.named_parameters() if p.requires_grad}
     # both ranks: one collective over the whole flat buffer per step, whichever way the step was served
-    replays = m.__dict__.get("_finetune_graph_replays", 0)
+    replays = TG.stats(m, TG.FINETUNE).replays
     mine_pat = torch.tensor([len(red.last_launched), red.last_launched[0][0], red.last_launched[-1][1], red.n_collectives],
                             dtype=torch.int64, device=dev)
     both = [torch.zeros_like(mine_pat) for _ in range(world)]

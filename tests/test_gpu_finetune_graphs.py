@@ -85,7 +85,7 @@ def _step(m, opt, feed, rows, ans, set_to_none=False):
 
 
 def _replays(m):
-    return m.__dict__.get("_finetune_graph_replays", 0)
+    return TG.stats(m, TG.FINETUNE).replays
 
 
 def _cache(m):
@@ -112,7 +112,7 @@ def test_replayed_finetune_step_equals_the_eager_step(golden, set_to_none):
             assert logits[-1].shape == (B, N_ANS)
         results.append((logits, _params(m), m.step_seed))
         if graphs:  # the two assertions that cannot hold without the feature
-            assert len(_cache(m)) == 2 and m.__dict__["_finetune_graph_captures"] == 2, list(_cache(m))
+            assert len(_cache(m)) == 2 and TG.stats(m, TG.FINETUNE).captures == 2, list(_cache(m))
             assert _replays(m) == 3
             assert m.finetune_graphs is True
         else:
@@ -197,7 +197,7 @@ def test_finetune_graph_edges(golden):
     m.train()
     opt = FusedAdam(m, lr=1e-3, betas=(0.9, 0.95))
     _step(m, opt, feed, rows, ans)
-    assert _replays(m) == n_rep + 1 and len(_cache(m)) == 1 and m.__dict__["_finetune_graph_captures"] == 1
+    assert _replays(m) == n_rep + 1 and len(_cache(m)) == 1 and TG.stats(m, TG.FINETUNE).captures == 1
 
 
 # ------------------------------------------------------------------------------------------------ 3. mc.candidate_scores
@@ -288,7 +288,7 @@ def test_shape_churn_switches_the_graphs_off_with_one_warning(golden):
             assert m.finetune_graphs is (B <= 12), B
     said = [w for w in seen if "finetune_graphs" in str(w.message)]
     assert len(said) == 1 and "13 distinct" in str(said[0].message), [str(w.message) for w in seen]
-    assert _replays(m) == 12 and not _cache(m) and m.__dict__.get("_finetune_graphs_auto_off") is True
+    assert _replays(m) == 12 and not _cache(m) and TG.stats(m, TG.FINETUNE).auto_off is True
     assert m.step_seed == 15
 
 
@@ -328,10 +328,61 @@ def test_finetune_graphs_100_replays(golden):
     bad = nf.cpu()
     assert int(bad.sum()) == 0, f"non-finite gradient in replay {int(torch.nonzero(bad)[0])}"
     assert not mism, mism
-    assert m.__dict__["_finetune_graph_captures"] == 1 and _replays(m) == n
+    assert TG.stats(m, TG.FINETUNE).captures == 1 and _replays(m) == n
 
 
-# ------------------------------------------------------------------------------------------------ 7. two ranks
+# ------------------------------------------------------------------------------------------------ 7. a released cache
+@pytest.mark.parametrize("route", TG.ROUTES, ids=lambda r: r.switch)
+def test_a_cache_popped_by_its_name_is_captured_again(golden, route):
+    """All three routes at B = 2, 10 video slots, 21 text tokens: two served calls, the route's cache popped from
+    `model.__dict__` by its name (what the benchmark does to release the graphs), the same feed again.  The third call
+    captures anew and is served; it returns what the second returned (inference: same weights, same feed) or what an eager
+    twin stepped alongside returns (training routes: loss / logits and the flat gradient buffer), bit for bit."""
+    a2tok = golden("G10_videoqa", raw=True)["a2tok"]
+    cfg, m = _live_model(a2tok)
+    setattr(m, route.switch, True)
+    st = TG.stats(m, route)
+    labelled = to_dev(synth_batch(cfg, B=2, L=21, seed=91))
+    feed, rows, ans = _batch(cfg, 2, 21, seed=91)
+    pfeed, prows = _padded(cfg, feed, rows)
+
+    def call(model, graphed):
+        """one call of the route's kind: its output, and the flat gradient it left"""
+        if route is TG.INFERENCE:
+            with torch.no_grad():
+                return model(logit_rows=rows, **feed)["logits"].clone(), None
+        model.zero_grad(set_to_none=False)
+        if route is TG.MLM:
+            out = model(mlm=True, **labelled).loss
+            out.backward()
+        else:
+            out = model(logit_rows=rows, **feed)["logits"] if graphed else model(logit_rows=prows, **pfeed)["logits"]
+            F.cross_entropy(out, ans).backward()
+        return out.detach().clone(), model.engine().flat_grad.clone()
+
+    if route is TG.INFERENCE:
+        m.eval()
+        twin = None
+    else:
+        _, twin = _live_model(a2tok)  # the eager run (the fine-tuning route: on the padded copy of the batch)
+    outs = []
+    for i in range(3):
+        if i == 2:
+            assert st.replays == 2 and len(m.__dict__.pop(route.cache)) == 1
+        outs.append(call(m, True))
+        if twin is not None:
+            ref = call(twin, False)
+            assert torch.equal(outs[-1][0], ref[0]) and torch.equal(outs[-1][1], ref[1]), i
+            assert ref[1].abs().max().item() > 0
+    assert len(m.__dict__[route.cache]) == 1 and st.replays == 3 and getattr(m, route.switch) is True
+    assert st.captures == (1 if route.budgeted else 0)  # (captured twice; a configuration seen before is not counted again)
+    if route is TG.INFERENCE:
+        assert torch.equal(outs[2][0], outs[1][0]) and outs[2][0].shape == (2, N_ANS)
+    else:
+        assert not torch.equal(outs[2][0], outs[1][0])  # (another step of the mask stream)
+
+
+# ------------------------------------------------------------------------------------------------ 8. two ranks
 CHILD_LIMIT_S = 240
 
 

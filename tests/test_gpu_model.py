@@ -1238,7 +1238,9 @@ def test_graphed_training_step_soak_300_replays():
             bad = nf[:i + 1].cpu()
             assert int(bad.sum()) == 0, f"non-finite gradient in replay {int(torch.nonzero(bad)[0])}"
     assert not mism, mism
-    assert m.__dict__.get("_train_graph_captures", 0) == 1
+    from frozenbilm_amd import train_graph as TG
+
+    assert TG.stats(m, TG.MLM).captures == 1
 
 
 def test_inference_shortcuts_change_nothing():

@@ -23,6 +23,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from frozenbilm_amd import train_graph as TG  # noqa: E402
 from frozenbilm_amd.optim import FusedAdam  # noqa: E402
 from oracle import deberta_oracle as O  # noqa: E402
 from tests.gpu_refs import ref_adam  # noqa: E402
@@ -385,7 +386,7 @@ def test_graphs_follow_the_live_set(golden, route):
                 loss.backward()
                 outs.append(loss.detach().clone())
             opt.step(clip_max_norm=1.0)
-            caps.append(m.__dict__.get("_finetune_graph_captures" if ft else "_train_graph_captures", 0))
+            caps.append(TG.stats(m, TG.FINETUNE if ft else TG.MLM).captures)
         res.append((outs, m.engine().flat.clone(), caps, getattr(m, route)))
     (o0, p0, c0, _), (o1, p1, c1, on) = res
     assert c0 == [0, 0, 0] and c1 == [1, 2, 2] and on is True, (c0, c1, on)

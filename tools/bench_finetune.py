@@ -40,6 +40,7 @@ import torch
 import torch.nn.functional as F
 
 from frozenbilm_amd import mc as P_mc
+from frozenbilm_amd import train_graph as TG
 from frozenbilm_amd import videoqa as P_vqa
 from frozenbilm_amd.model import DebertaV2Config, DebertaV2ForMaskedLM
 from frozenbilm_amd.optim import FusedAdam
@@ -201,8 +202,8 @@ def workload(name):
            "rows": {"padded": n * S, "packed": rows_packed, "share": round(rows_packed / (n * S), 3)},
            "step_ms": alternate_stats(legs, a.steps, a.warmup), "host_ms": host_issue_stats(legs, a.steps),
            "peak_mb": peak_memory(legs),
-           "graph_captures": m.__dict__.get("_finetune_graph_captures", 0),
-           "graph_replays": m.__dict__.get("_finetune_graph_replays", 0)}
+           "graph_captures": TG.stats(m, TG.FINETUNE).captures,
+           "graph_replays": TG.stats(m, TG.FINETUNE).replays}
     if "full" in legs:
         full = res["step_ms"]["full"]["median"]
         res["speedup_vs_full"] = {k: round(full / v["median"], 3) for k, v in res["step_ms"].items() if k != "full"}

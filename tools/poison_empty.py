@@ -53,6 +53,7 @@ if not args.no_poison:
 sys.argv = ["bench.py"]
 import bench  # noqa: E402
 from frozenbilm_amd import lib as L  # noqa: E402
+from frozenbilm_amd import train_graph as TG  # noqa: E402
 from frozenbilm_amd.model import DebertaV2Config, DebertaV2ForMaskedLM  # noqa: E402
 from frozenbilm_amd.optim import FusedAdam  # noqa: E402
 
@@ -185,10 +186,10 @@ for cyc, ph in ((c, p) for c in range(args.cycles) for p in phases):
         for i in range(4):
             step(batch, f"graphed {i}" + (" last" if i == 3 else ""))
         model.training_graphs = False
-        model.__dict__.pop("_train_graphs", None)
+        TG.reset(model, TG.MLM)
     elif ph == "graphed_b1":
         # bench.py's `graphed_step` leg exactly: B=32 graph (capture + replays), B=1 graph (capture + replays), B=32 replays again
-        model.__dict__["_train_graph_captures"] = 0
+        TG.reset(model, TG.MLM)
         model.training_graphs = True
         dense = (cyc % 2 == 1) or not args.sparse_checks
         for part, b, n in (("B32", batch, 8), ("B1", small, 8), ("B32 again", batch, 4)):
@@ -205,7 +206,7 @@ for cyc, ph in ((c, p) for c in range(args.cycles) for p in phases):
                 else:
                     step(b, f"graphed_b1 c{cyc} {part} {i}" + (" last" if last else ""))
         model.training_graphs = False
-        model.__dict__.pop("_train_graphs", None)
+        TG.reset(model, TG.MLM)
     elif ph == "packed":
         model.packed_rows = True
         try:

@@ -31,6 +31,7 @@ args = ap.parse_args()
 sys.argv = ["bench.py"]
 import bench  # noqa: E402
 from frozenbilm_amd import lib as L  # noqa: E402
+from frozenbilm_amd import train_graph as TG  # noqa: E402
 from frozenbilm_amd.model import DebertaV2Config, DebertaV2ForMaskedLM  # noqa: E402
 from frozenbilm_amd.optim import FusedAdam  # noqa: E402
 
@@ -131,7 +132,7 @@ for i in range(n):
 dt = time.time() - t0
 res = {"replays": n, "layers": args.layers, "batch": B, "b1_every": args.b1_every, "seconds": round(dt, 1),
        "ms_per_replayed_step": round(1e3 * dt / n, 2), "nonfinite_findings": findings, "eager_checks": eager_checks,
-       "eager_mismatches": eager_mismatch, "b1_nonfinite": b1_bad, "captures": model.__dict__.get("_train_graph_captures", 0)}
+       "eager_mismatches": eager_mismatch, "b1_nonfinite": b1_bad, "captures": TG.stats(model, TG.MLM).captures}
 print(json.dumps(res), flush=True)
 os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
 with open(args.out, "w") as f:
