@@ -36,6 +36,7 @@ import torch
 from . import lib as L
 from .engine import BF16, F32, Engine, NormRef, Packing, Run, Stream, _ru, _StepFn, check_logit_rows
 from .live_set import LiveSetMixin
+from .predict import check_topk, of_call as predictions_of_call
 
 
 @dataclass
@@ -243,6 +244,7 @@ class BertEngine(LiveSetMixin):
     def run(self, input_ids, attention_mask, video, video_mask, labels, mlm, want_hidden, logit_rows=None):
         m = self.m
         train = m.training
+        k_pred = check_topk(getattr(m, "predict_topk", 0))  # opt-in `model.predict_topk`, read per call (as Engine.run does)
         if input_ids.device != self.dev:
             raise RuntimeError(f"inputs must be on {self.dev}")
         if attention_mask is None:
@@ -315,6 +317,8 @@ class BertEngine(LiveSetMixin):
             res = {"logits": logits[:, :Vout], "loss": None, "run": run}
         else:
             res = {"logits": logits.view(B, S, -1)[:, :, :Vout], "loss": None, "run": run}
+        if k_pred:
+            res["predictions"] = predictions_of_call(run, logits, k_pred, rows_labelled, logit_rows)
         if want_hidden:
             res["hidden_states"] = run.hidden_out
         if need_grad:

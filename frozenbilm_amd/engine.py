@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .predict import check_topk, of_call as predictions_of_call
 from .live_set import REL_LN, LiveSetMixin, flat_layout, stage_plan
 from .attn_bwd import ATTN_SCALE, _relidx_range, disent_attn_bwd, pos_chain_buffers, pos_table_grads_batched
 from .model.relpos import rel_index_vector
@@ -494,6 +495,7 @@ class Engine(LiveSetMixin):
         """inputs_embeds: float [B, L, H] in place of E[input_ids] (input_ids is then None; model/deberta.py:1204-1225)."""
         m = self.m
         train = m.training
+        k_pred = check_topk(getattr(m, "predict_topk", 0))  # opt-in `model.predict_topk`, read per call (ValueError here)
         text = input_ids if inputs_embeds is None else inputs_embeds
         if text.device != self.dev:
             raise RuntimeError(f"inputs must be on {self.dev}")
@@ -589,6 +591,9 @@ class Engine(LiveSetMixin):
             res = {"logits": logits[:, :Vout], "loss": None, "run": run}
         else:  # (packed rows: `logits` is the [B*S, V] grid tensor here too -- allocated in _forward, filled on access)
             res = {"logits": logits.view(B, S, -1)[:, :, :Vout] if logits is not None else None, "loss": None, "run": run}
+        if k_pred:  # top-k / label rank / NLL of the rows this call already holds logits for (predict.py); detached
+            res["predictions"] = predictions_of_call(run, logits, k_pred, rows_labelled if full_labels is not None else None,
+                                                     logit_rows)
         if want_hidden:
             res["hidden_states"] = run.hidden_out
         if want_attn:

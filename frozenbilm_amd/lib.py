@@ -64,6 +64,7 @@ SIGNATURES = _header_signatures("fbl.h")
 MHA_SIGNATURES = _header_signatures("fbl_mha.h")      # the BERT variant's fused attention
 QROWS_SIGNATURES = _header_signatures("fbl_qrows.h")  # the enhanced mask decoder's attention on selected query rows
 LIVE_SIGNATURES = _header_signatures("fbl_live.h")    # clip norm and Adam over a live set of the flat trainable buffer
+PREDICT_SIGNATURES = _header_signatures("fbl_predict.h")  # top-k / label rank / NLL of selected rows from their logits
 
 _LIB = None
 
@@ -80,7 +81,7 @@ def load(path: Optional[str] = None):
             "there is no CPU/eager fallback")
     lib = C.CDLL(p)
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
-                              *LIVE_SIGNATURES.items()):
+                              *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -713,6 +714,39 @@ def ce_bwd_rows(logits, labels, rows, V, Vp, row_lse, loss_sum_cnt, gscale, dlog
         gscale = 1.0
     _chk(load().fbl_ce_bwd_rows(_p(logits), ldv, _p(labels), _p(rows), rows.numel(), V, Vp, _p(row_lse),
                                 _p(loss_sum_cnt), float(gscale), _p(gdev), _p(dlogits), _stream()), "fbl_ce_bwd_rows")
+
+
+PREDICT_MAX_K = 16  # FBL_PREDICT_MAX_K of include/fbl_predict.h
+
+
+def row_predict(logits, V, k, labels=None, row_lse=None):
+    """Top-k ids / log-probabilities of every row of `logits` fp32 [R, ldv] (columns V.. are never used), in the total order of
+    include/fbl_predict.h; with `labels` int64 [R] also the label's rank and the row's NLL.  `row_lse` fp32 [R]: the rows'
+    log-sum-exp when the caller has it (fbl_ce_fwd wrote it), else it is computed in the same pass.
+    Returns (topk_ids int32 [R, k], topk_logprob fp32 [R, k], label_rank int32 [R] | None, row_nll fp32 [R] | None)."""
+    ldv = _rows2d(logits, "logits")
+    _req(logits, torch.float32, "logits")
+    R, dev = logits.shape[0], logits.device
+    if not 1 <= int(k) <= PREDICT_MAX_K:
+        raise ValueError(f"k = {k}: fbl_row_predict takes 1..{PREDICT_MAX_K}")
+    if labels is not None:
+        _req(labels, torch.int64, "labels")
+        assert labels.is_contiguous() and labels.numel() == R
+    if row_lse is not None:
+        _req(row_lse, torch.float32, "row_lse")
+        assert row_lse.is_contiguous() and row_lse.numel() == R
+    ids = torch.empty(R, k, dtype=torch.int32, device=dev)
+    lp = torch.empty(R, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(R, dtype=torch.int32, device=dev) if labels is not None else None
+    nll = torch.empty(R, dtype=torch.float32, device=dev) if labels is not None else None
+    h = load()
+    nbytes = h.fbl_row_predict_ws_bytes(R, int(V), int(k))
+    if nbytes < 0:
+        _chk(nbytes, "fbl_row_predict_ws_bytes")
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=dev)
+    _chk(h.fbl_row_predict(_p(logits), ldv, R, int(V), int(k), _p(labels), _p(row_lse), _p(ids), _p(lp), _p(rank), _p(nll),
+                           _p(ws), nbytes, _stream()), "fbl_row_predict")
+    return ids, lp, rank, nll
 
 
 def gather_rows_bf16(x, rows, out):

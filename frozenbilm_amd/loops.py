@@ -48,26 +48,39 @@ class LossLog:
     Under data parallelism with a `GradReducer` the loss rides in front of the first gradient bucket (parallel.py: no
     collective and no synchronisation of its own); without one, `dist.reduce_dict` as in the reference.  `log(loss)` keeps
     the reference's literal order (read, then backward) for callers that want it, and ``args.delayed_loss_check`` (opt-in)
-    moves the read to the NEXT step's call (evaluation loops do that by default: they have no update to protect)."""
+    moves the read to the NEXT step's call (evaluation loops do that by default: they have no update to protect).
+
+    `extras` (optional, on `begin` and on the call): a dict of further scalars of the step that are only LOGGED -- they travel
+    with the loss (the same staging copy, the same scalar slot of the reducer, the same rank average) and reach the meters
+    under their own names, but they are neither part of the `loss=` sum nor of the non-finite check.  The entry
+    ``LossLog.WEIGHT`` is not logged: it is the weight the other extras were multiplied by (1 or 0 per rank: "this batch has
+    such rows"); the averaged extras are divided by the averaged weight, and a step whose weight is 0 updates none of them."""
+
+    WEIGHT = "_weight"
 
     def __init__(self, run: "EpochRunner", name: str, stop_on_nonfinite: bool = True, delayed: bool = False, reducer=None):
         self.run, self.name, self.stop, self.delayed = run, name, stop_on_nonfinite, delayed
         self.reducer = reducer if (reducer is not None and getattr(reducer, "carries_scalars", False)) else None
         self.pending = None
         self._staged_loss = None
+        self._staged_extras = {}
         self._host = None
         self._flip = 0
         run.loss_log = self
 
-    def _emit(self, reduced_host):
+    def _emit(self, reduced_host, extra_keys=()):
+        extras = {k: reduced_host.pop(k) for k in extra_keys}
         value = float(sum(reduced_host.values()))
         if self.stop and not math.isfinite(value):
             print("Loss is {}, stopping training".format(value))
             print(reduced_host)
             sys.exit(1)
         self.run.log(loss=value, **reduced_host)
+        weight = extras.pop(self.WEIGHT, 1.0)
+        if extras and weight > 0:
+            self.run.log(**{k: v / weight for k, v in extras.items()})
 
-    def _stage(self, keys, values):
+    def _stage(self, keys, values, extra_keys=()):
         """asynchronous copy of the (already reduced) scalars to pinned memory; two alternating buffers"""
         if self._host is None:
             self._host = [torch.empty(8, dtype=torch.float32).pin_memory() for _ in range(2)]
@@ -76,32 +89,37 @@ class LossLog:
         host[: len(keys)].copy_(torch.stack([v.detach().float().reshape(()) for v in values]), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self.pending = ("host", keys, host, ev)
+        self.pending = ("host", keys, host, ev, extra_keys)
 
-    def __call__(self, loss):
+    def __call__(self, loss, extras=None):
         """the reference's order: reduce, read on the host now (or, delayed, when the next step calls)"""
-        reduced = dist.reduce_dict({self.name: loss})
+        extras = extras or {}
+        reduced = dist.reduce_dict({self.name: loss, **extras})
         if not (self.delayed and all(torch.is_tensor(v) and v.is_cuda for v in reduced.values())):
-            self._emit({k: (v.item() if torch.is_tensor(v) else float(v)) for k, v in reduced.items()})
+            self._emit({k: (v.item() if torch.is_tensor(v) else float(v)) for k, v in reduced.items()}, tuple(extras))
             return
         self.flush()
         keys = list(reduced)
-        self._stage(keys, [reduced[k] for k in keys])
+        self._stage(keys, [reduced[k] for k in keys], tuple(extras))
 
-    def begin(self, loss):
+    def begin(self, loss, extras=None):
         """stage the loss of this step; `check()` reads it after the backward has been enqueued"""
         self.flush()
+        extras = extras or {}
         if not (torch.is_tensor(loss) and loss.is_cuda):
-            self(loss)  # host-side losses (test doubles): nothing to overlap
+            self(loss, extras)  # host-side losses (test doubles): nothing to overlap
             return
         if self.reducer is not None and dist.get_world_size() > 1:
-            self.reducer.stage_scalars(loss.reshape(1))  # leaves with the first gradient bucket of this step's backward
-            self._staged_loss = loss.detach()
-            self.pending = ("reducer", [self.name])
+            # leaves with the first gradient bucket of this step's backward
+            scalars = [loss, *extras.values()]
+            self.reducer.stage_scalars(torch.stack([v.detach().float().reshape(()) for v in scalars]) if extras
+                                       else loss.reshape(1))
+            self._staged_loss, self._staged_extras = loss.detach(), {k: v.detach() for k, v in extras.items()}
+            self.pending = ("reducer", [self.name, *extras], tuple(extras))
             return
-        reduced = dist.reduce_dict({self.name: loss})
+        reduced = dist.reduce_dict({self.name: loss, **extras})
         keys = list(reduced)
-        self._stage(keys, [reduced[k] for k in keys])
+        self._stage(keys, [reduced[k] for k in keys], tuple(extras))
 
     def check(self):
         self.flush()
@@ -119,14 +137,14 @@ class LossLog:
                 loss = self._staged_loss
                 if loss is None:
                     return
-                reduced = dist.reduce_dict({self.name: loss})
-                self._emit({k: float(v.item()) for k, v in reduced.items()})
+                reduced = dist.reduce_dict({self.name: loss, **self._staged_extras})
+                self._emit({k: float(v.item()) for k, v in reduced.items()}, pend[2])
                 return
-            self._emit(dict(zip(pend[1], vals)))
+            self._emit(dict(zip(pend[1], vals)), pend[2])
             return
-        _, keys, host, ev = pend
+        _, keys, host, ev, extra_keys = pend
         ev.synchronize()
-        self._emit({k: float(host[i]) for i, k in enumerate(keys)})
+        self._emit({k: float(host[i]) for i, k in enumerate(keys)}, extra_keys)
 
 
 def frozen_weights(model):
@@ -151,15 +169,15 @@ def optimizer_step(loss, optimizer, model, max_norm, reducer=None, check=None):
     optimizer.step()
 
 
-def logged_step(log: "LossLog", loss, optimizer, model, max_norm, reducer=None):
+def logged_step(log: "LossLog", loss, optimizer, model, max_norm, reducer=None, extras=None):
     """One training step with the reference's loss bookkeeping (main.py:70-86, videoqa.py:84-101, mc.py:94-113): by default
     the backward is enqueued before the host reads the loss (no update after a non-finite loss, see LossLog); with the
     opt-in ``delayed_loss_check`` the loss is read when the next step calls."""
     if log.delayed:
-        log(loss)
+        log(loss, extras)
         optimizer_step(loss, optimizer, model, max_norm, reducer=reducer)
     else:
-        log.begin(loss)
+        log.begin(loss, extras)
         optimizer_step(loss, optimizer, model, max_norm, reducer=reducer, check=log.check)
 
 

@@ -128,6 +128,7 @@ class BertForMaskedLM(nn.Module):
         self.finetune_graphs = False
         self.packed_rows = False
         self.decoder_rows = False  # accepted, does nothing: this model has no enhanced mask decoder
+        self.predict_topk = 0  # opt-in, as on the DeBERTa model: k in 1..16 makes every call return `predictions`
         self._weights_frozen = 0
         self._reducer = None
         self.step_seed = 0
@@ -218,7 +219,8 @@ class BertForMaskedLM(nn.Module):
                 raise NotImplementedError("only the default positions 0..S-1 are on the FrozenBiLM hot path")
         eng = self.engine()
         res = eng.run(input_ids, attention_mask, video, video_mask, labels, mlm, bool(output_hidden_states), logit_rows=logit_rows)
-        out = MaskedLMOutput(loss=res["loss"], logits=res["logits"], hidden_states=res.get("hidden_states"), attentions=None)
+        out = MaskedLMOutput(loss=res["loss"], logits=res["logits"], hidden_states=res.get("hidden_states"), attentions=None,
+                             predictions=res.get("predictions"))
         run = res["run"]
         out.__dict__["_run"] = run
         if run.logits_pending:

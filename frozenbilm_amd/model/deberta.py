@@ -32,7 +32,10 @@ class MaskedLMOutput(dict):
     When a loss was asked for (``labels`` given) the forward computes only the labelled rows of the prediction head;
     the full ``logits`` tensor is allocated -- and wired into the autograd graph like the reference's -- but its
     contents are produced on first access, by any accessor of this mapping (``out.logits``, ``out["logits"]``,
-    ``out[1]``, ``get``, ``values``, ``items``, iteration / ``dict(out)`` / ``**out``)."""
+    ``out[1]``, ``get``, ``values``, ``items``, iteration / ``dict(out)`` / ``**out``).
+
+    ``predictions`` (``out.predictions`` / ``out["predictions"]``): None unless ``model.predict_topk`` > 0, then a
+    ``predict.Predictions``; an extension, not part of the ``return_dict=False`` tuple.  Reading it does not fill the logits."""
 
     _fill = None  # callable that materialises the logits, or None
 
@@ -239,6 +242,11 @@ class DebertaV2ForMaskedLM(nn.Module):
         self.packed_rows = False
         # opt-in: the two enhanced-mask-decoder passes, the head and their backward on the selected rows only (engine.py)
         self.decoder_rows = False
+        # opt-in, read per call: an int k in 1..16 makes every call return `predictions` (predict.Predictions) -- top-k ids and
+        # log-probabilities of the rows the call forms logits for anyway (the labelled rows, the `logit_rows`, else every row),
+        # with the label's rank and the row's NLL on a labelled call.  One extra pass over those [R, V] logits; never fills the
+        # full [B*S, V] logits.  Loss, logits and gradients are those of the same call with 0 (off); such a call runs eagerly.
+        self.predict_topk = 0
         self._weights_frozen = 0  # nesting depth of weights_frozen(): inference forwards may reuse the packed operands
         self._reducer = None  # parallel.GradReducer attached to this model (survives engine rebuilds)
         self.step_seed = 0  # advanced every training forward; keys the counter-based dropout
@@ -413,6 +421,9 @@ class DebertaV2ForMaskedLM(nn.Module):
                                  f"(got {tuple(getattr(inputs_embeds, 'shape', ()))})")
             if not inputs_embeds.is_floating_point():
                 raise ValueError(f"inputs_embeds must have a floating dtype (got {inputs_embeds.dtype})")
+        from ..predict import check_topk
+
+        check_topk(self.predict_topk)  # (ValueError at the call, whichever route would serve it)
         eng = self.engine()
         from .. import train_graph as TG  # (the launch graphs, opt-in: which calls they serve is TG.route_for's to say)
 
@@ -429,7 +440,7 @@ class DebertaV2ForMaskedLM(nn.Module):
             res = eng.run(input_ids, attention_mask, video, video_mask, labels, mlm, output_hidden_states,
                           logit_rows=logit_rows, want_attn=bool(output_attentions), inputs_embeds=inputs_embeds)
         out = MaskedLMOutput(loss=res["loss"], logits=res["logits"], hidden_states=res.get("hidden_states"),
-                             attentions=res.get("attentions"))
+                             attentions=res.get("attentions"), predictions=res.get("predictions"))
         run = res.get("run")
         out.__dict__["_run"] = run  # (tests read the saved bottleneck activations through this)
         if run is not None and run.logits_pending:
