@@ -3,6 +3,7 @@
 #include "fbl_common.h"
 #include "../../include/fbl.h"
 #include "../../include/fbl_live.h"
+#include "../../include/fbl_groups.h"
 
 namespace {
 
@@ -873,6 +874,78 @@ __global__ __launch_bounds__(256) void adam_flat_live_kernel(float* p, const flo
     *(f32x4*)(p + a) = po;
   }
 }
+// ---- Adam over PARAMETER GROUPS (include/fbl_groups.h): adam_flat_live_kernel's walk over the compact index space, with a
+// third column in the table -- the group of each segment -- and the groups' hyper-parameters in the argument block
+// (record = {lr, b1, b2, eps, wd, decoupled, bc1, bc2}).  The block copies the records to LDS once (a flat, lane-indexed
+// read of the kernarg segment: no private copy of the table), then every lane reads the record of its segment's group: two
+// 16-byte LDS reads, the same address across a wave except at segment borders.
+constexpr int ADAM_REC = 8;
+struct AdamGroupArgs {
+  float rec[FBL_ADAM_MAX_GROUPS * ADAM_REC];
+};
+struct GroupTab {
+  long begin[LIVE_MAX_RANGES], cum[LIVE_MAX_RANGES];
+  int group[LIVE_MAX_RANGES];
+};
+__global__ __launch_bounds__(256) void adam_flat_groups_kernel(float* p, const float* g, float* m, float* v, long n,
+                                                               const int64_t* tab, int ng, AdamGroupArgs a,
+                                                               const float* sumsq, float max_norm, float grad_scale) {
+  __shared__ GroupTab t;
+  __shared__ __attribute__((aligned(16))) float rec[FBL_ADAM_MAX_GROUPS * ADAM_REC];
+  long ns = tab[0];
+  ns = ns < 0 ? 0 : (ns > LIVE_MAX_RANGES ? LIVE_MAX_RANGES : ns);
+  for (int s = threadIdx.x; s < ns; s += blockDim.x) {
+    t.begin[s] = tab[2 + 3 * s];
+    t.cum[s] = tab[3 + 3 * s];
+    const long gs = tab[4 + 3 * s];
+    t.group[s] = (gs < 0 || gs >= ng) ? -1 : (int)gs;
+  }
+  for (int i = threadIdx.x; i < ng * ADAM_REC; i += blockDim.x) rec[i] = a.rec[i];
+  __syncthreads();
+  const long n_live = ns > 0 ? tab[1] : 0;
+  const int nr = (int)ns;
+  float clip = grad_scale;
+  if (sumsq && max_norm > 0.f) {
+    const float norm = sqrtf(sumsq[0]) * grad_scale;
+    clip *= fminf(1.0f, max_norm / (norm + 1e-6f));
+  }
+  for (long c = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; c < n_live; c += (long)gridDim.x * blockDim.x * 4) {
+    int lo = 0, hi = nr;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (t.cum[mid] <= c) lo = mid; else hi = mid;
+    }
+    const long at = t.begin[lo] + (c - t.cum[lo]);
+    const int grp = t.group[lo];
+    if (at < 0 || at + 4 > n || (at & 3) || grp < 0) continue;  // (a malformed table, a group out of range: nothing is touched)
+    const f32x4 h0 = *(const f32x4*)(rec + grp * ADAM_REC), h1 = *(const f32x4*)(rec + grp * ADAM_REC + 4);
+    const float lr = h0[0], b1 = h0[1], b2 = h0[2], eps = h0[3], wd = h1[0], bc1 = h1[2], bc2 = h1[3];
+    const bool decoupled = h1[1] != 0.f;
+    const f32x4 gv = *(const f32x4*)(g + at), pv = *(const f32x4*)(p + at);
+    const f32x4 mv = *(const f32x4*)(m + at), vv = *(const f32x4*)(v + at);
+    f32x4 po, mo, vo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      // Coupled: adam_flat_live_kernel's arithmetic, instruction for instruction (contraction off, the one fma written out):
+      // with the same hyper-parameters the bits of fbl_adam_flat.  Decoupled (AdamW): the parameter shrinks by 1 - lr * wd
+      // first and the gradient carries no decay term; the same sequence otherwise.  tests/test_gpu_adam_groups.py.
+#pragma clang fp contract(off)
+      float gi = gv[e] * clip;
+      float pi = pv[e];
+      if (decoupled) pi = pi * (1.f - lr * wd);
+      else if (wd != 0.f) gi = gi + wd * pi;
+      const float mi = b1 * mv[e] + (1.f - b1) * gi;
+      const float vi = b2 * vv[e] + ((1.f - b2) * gi) * gi;
+      mo[e] = mi;
+      vo[e] = vi;
+      const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+      po[e] = __builtin_fmaf(-(lr / bc1), mi / denom, pi);
+    }
+    *(f32x4*)(m + at) = mo;
+    *(f32x4*)(v + at) = vo;
+    *(f32x4*)(p + at) = po;
+  }
+}
 __global__ void cast_bf16_kernel(const float* in, bf16* out, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = f2bf(in[i]);
 }
@@ -1232,6 +1305,27 @@ extern "C" int fbl_adam_flat_live(float* p, const float* g, float* m, float* v, 
   const float bc2 = 1.0f - powf(beta2, (float)step);
   hipLaunchKernelGGL(adam_flat_live_kernel, dim3(grid1d(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      (long)n, ranges, lr, beta1, beta2, eps, weight_decay, bc1, bc2, sumsq, max_norm, grad_scale);
+  FBL_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- include/fbl_groups.h
+extern "C" int fbl_adam_flat_groups(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* segs, int n_groups,
+                                    const float* hyper, int step, const float* sumsq, float max_norm, float grad_scale,
+                                    void* stream) {
+  if (!p || !g || !m || !v || !segs || !hyper || n_groups < 1 || n_groups > FBL_ADAM_MAX_GROUPS) return FBL_ERR_ARG;
+  if ((n & 7) || !live_aligned(p) || !live_aligned(g) || !live_aligned(m) || !live_aligned(v)) return FBL_ERR_ALIGN;
+  if (n <= 0) return 0;
+  AdamGroupArgs a{};
+  for (int k = 0; k < n_groups; ++k) {
+    const float* h = hyper + k * FBL_ADAM_GROUP_FLOATS;
+    float* r = a.rec + k * ADAM_REC;
+    for (int j = 0; j < FBL_ADAM_GROUP_FLOATS; ++j) r[j] = h[j];
+    r[6] = 1.0f - powf(h[1], (float)step);  // bc1, bc2: as fbl_adam_flat forms them
+    r[7] = 1.0f - powf(h[2], (float)step);
+  }
+  hipLaunchKernelGGL(adam_flat_groups_kernel, dim3(grid1d(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (long)n, segs, n_groups, a, sumsq, max_norm, grad_scale);
   FBL_CHECK_LAUNCH();
   return 0;
 }

@@ -65,6 +65,7 @@ MHA_SIGNATURES = _header_signatures("fbl_mha.h")      # the BERT variant's fused
 QROWS_SIGNATURES = _header_signatures("fbl_qrows.h")  # the enhanced mask decoder's attention on selected query rows
 LIVE_SIGNATURES = _header_signatures("fbl_live.h")    # clip norm and Adam over a live set of the flat trainable buffer
 PREDICT_SIGNATURES = _header_signatures("fbl_predict.h")  # top-k / label rank / NLL of selected rows from their logits
+GROUP_SIGNATURES = _header_signatures("fbl_groups.h")  # Adam over parameter groups of the flat trainable buffer
 
 _LIB = None
 
@@ -81,7 +82,7 @@ def load(path: Optional[str] = None):
             "there is no CPU/eager fallback")
     lib = C.CDLL(p)
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
-                              *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items()):
+                              *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -809,6 +810,52 @@ def adam_flat_live(p, g, m, v, table, lr, beta1, beta2, eps, weight_decay, step,
     _chk(load().fbl_adam_flat_live(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(table), float(lr), float(beta1), float(beta2),
                                    float(eps), float(weight_decay), int(step), _p(sumsq_t), float(max_norm), float(grad_scale),
                                    _stream()), "fbl_adam_flat_live")
+
+
+ADAM_MAX_GROUPS = 64   # parameter groups fbl_adam_flat_groups takes (include/fbl_groups.h FBL_ADAM_MAX_GROUPS)
+ADAM_GROUP_FLOATS = 6  # floats of one hyper-parameter record: lr, beta1, beta2, eps, weight_decay, decoupled
+
+
+def group_table(segments, n: int, device, n_groups: int = ADAM_MAX_GROUPS) -> torch.Tensor:
+    """The device table of include/fbl_groups.h for `segments` = [(begin, end, group), ..] inside a flat buffer of n elements;
+    refuses anything but sorted, disjoint, non-empty, 8-aligned segments with group ids in [0, n_groups) (the kernel trusts
+    the table it is given)."""
+    if len(segments) > LIVE_MAX_RANGES:
+        raise ValueError(f"{len(segments)} segments: the kernel takes {LIVE_MAX_RANGES}")
+    if not 1 <= n_groups <= ADAM_MAX_GROUPS:
+        raise ValueError(f"{n_groups} parameter groups: the kernel takes 1 .. {ADAM_MAX_GROUPS}")
+    tab, cum, last = [len(segments), 0], 0, 0
+    for b, e, k in segments:
+        if b < last or e <= b or e > n or b % 8 or e % 8:
+            raise ValueError(f"segment [{b}, {e}) of {n}: segments must be sorted, disjoint, non-empty and 8-aligned")
+        if not 0 <= k < n_groups:
+            raise ValueError(f"segment [{b}, {e}): group {k} outside [0, {n_groups})")
+        tab += [b, cum, k]
+        cum += e - b
+        last = e
+    tab[1] = cum
+    return torch.tensor(tab, dtype=torch.int64, device=device)
+
+
+def adam_hyper(groups):
+    """the host array of hyper-parameter records fbl_adam_flat_groups reads, from [(lr, beta1, beta2, eps, weight_decay,
+    decoupled), ..]"""
+    if not 1 <= len(groups) <= ADAM_MAX_GROUPS:
+        raise ValueError(f"{len(groups)} parameter groups: the kernel takes 1 .. {ADAM_MAX_GROUPS}")
+    flat = []
+    for lr, b1, b2, eps, wd, dec in groups:
+        flat += [float(lr), float(b1), float(b2), float(eps), float(wd), 1.0 if dec else 0.0]
+    return (C.c_float * len(flat))(*flat)
+
+
+def adam_flat_groups(p, g, m, v, table, groups, step, sumsq_t=None, max_norm=0.0, grad_scale=1.0):
+    """One Adam step over the segments of `table` (group_table); groups: [(lr, beta1, beta2, eps, weight_decay, decoupled), ..],
+    one record per parameter group (or the array adam_hyper made of them)."""
+    _req(table, torch.int64, "table")
+    hyper = groups if isinstance(groups, C.Array) else adam_hyper(groups)
+    _chk(load().fbl_adam_flat_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(table), len(hyper) // ADAM_GROUP_FLOATS, hyper,
+                                     int(step), _p(sumsq_t), float(max_norm), float(grad_scale), _stream()),
+         "fbl_adam_flat_groups")
 
 
 def cast_bf16(x, out):

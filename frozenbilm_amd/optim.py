@@ -20,25 +20,86 @@ own step 1; with the reference's betas the two agree after a few dozen steps).  
 not count.  ``state_dict()`` exports states only for parameters that have been updated at least once, as torch does.  With
 every flag untouched the step issues the two launches it always issued (fbl_sumsq, fbl_adam_flat); otherwise their live-set
 twins (include/fbl_live.h) over a device table of ranges -- two launches too, however the set is cut up.
+
+Parameter groups.  ``param_groups=[{"params": [...], "lr": .., "betas": .., "eps": .., "weight_decay": ..,
+"decoupled_weight_decay": ..}, ...]`` as torch takes them: ``params`` holds parameter names, ``fnmatch`` patterns over the names
+or the tensors themselves; a key a group leaves out inherits the constructor's value; every trainable-by-construction parameter
+lands in exactly one group and what no group names joins group 0 (frozenbilm_amd/param_groups.py).  ``decoupled_weight_decay``
+(torch >= 2.7's own key; also a constructor keyword, the default of every group) makes a group's decay AdamW's:
+``p <- p * (1 - lr * wd)``, then Adam with no decay term in the gradient.  ``lr_scale`` gives a group the rate
+``param_groups[0]["lr"] * lr_scale``, read at every ``step()`` (and written back to the group's ``lr``), so ``adjust_learning_rate``,
+which writes ``param_groups[0]["lr"]`` only, moves every group; a group with both ``lr`` and ``lr_scale`` is refused, and so is
+``lr_scale`` on group 0.  ``layerwise_param_groups(model, decay)`` builds the groups of layer-wise rate decay with no weight decay
+on LayerNorms and biases.  The hyper-parameters are read from the group dicts at every step.  Everything above holds per group:
+ONE step counter, ONE clip norm over the live elements of all groups, a dead parameter untouched in whatever group it sits.
+With one group and coupled decay the step is the path described above, launch for launch; otherwise it is the norm (fbl_sumsq or
+fbl_sumsq_live) plus ONE fbl_adam_flat_groups (include/fbl_groups.h) over a device table of (live run, group) segments, cached per
+live set.  Checkpoints speak torch's multi-group schema: the parameter indices run through the groups in order.
 """
 from __future__ import annotations
 
 import torch
 
 from . import lib as L
+from . import param_groups as PG
+
+
+def layerwise_param_groups(model, decay: float, no_decay=("LayerNorm", "bias")):
+    """``param_groups`` for layer-wise learning-rate decay (param_groups.layerwise_groups): a stage i steps below the top trains
+    at ``decay**i`` of group 0's rate; names holding a ``no_decay`` substring get ``weight_decay = 0``."""
+    return PG.layerwise_groups(model.trainable_names(), model.config.num_hidden_layers, decay, no_decay)
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.0, *, param_groups=None,
+                 decoupled_weight_decay=False):
         self.model = model
-        cons = set(model.trainable_names())
-        params = [p for n, p in model.named_parameters() if n in cons]
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        names = model.trainable_names()
+        cons = set(names)
+        named = {n: p for n, p in model.named_parameters() if n in cons}
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if param_groups is None and not decoupled_weight_decay:
+            super().__init__([named[n] for n in names], defaults)
+        else:
+            spec = [dict(g) for g in (param_groups or [])] or [dict(params=[])]
+            PG.check_groups(spec)
+            members = PG.resolve(spec, names, {id(p): n for n, p in named.items()})
+            for g, mem in zip(spec, members):
+                g["params"] = [named[n] for n in mem]
+            defaults["decoupled_weight_decay"] = bool(decoupled_weight_decay)
+            super().__init__(spec, defaults)
+            self._sync_lr()
         self._ever = set()  # names of the parameters that a step has updated (or whose state a checkpoint brought)
         self._m = self._v = None
         self._step = 0
         self._ss = None
         self._ss_ws = None
+        self._seg_tables = {}  # "engine" -> the engine the tables belong to; (device, live_version) -> table of include/fbl_groups.h
+
+    def _sync_lr(self):
+        """a group with lr_scale follows group 0: its `lr` is what the next step uses"""
+        for g, lr in zip(self.param_groups, PG.learning_rates(self.param_groups)):
+            g["lr"] = lr
+
+    def _plain(self) -> bool:
+        """one group with coupled decay: the step of fbl_adam_flat / fbl_adam_flat_live"""
+        return len(self.param_groups) == 1 and not self.param_groups[0].get("decoupled_weight_decay", False)
+
+    def _segment_table(self, eng):
+        if self._seg_tables.get("engine") is not eng:  # (live_version numbers the live sets of ONE engine)
+            self._seg_tables = {"engine": eng}
+        key = (str(eng.flat.device), eng.live_version)
+        t = self._seg_tables.get(key)
+        if t is None:
+            gof = {}
+            name_of = {id(eng.named[n]): n for n in eng.order}
+            for k, g in enumerate(self.param_groups):
+                for p in g["params"]:
+                    gof[name_of[id(p)]] = k
+            numel = {n: eng.named[n].numel() for n in eng.order}
+            segs = PG.segments(eng.order, eng.offsets, numel, eng.live_order, gof)
+            t = self._seg_tables[key] = L.group_table(segs, eng.flat.numel(), eng.flat.device, len(self.param_groups))
+        return t
 
     def zero_grad(self, set_to_none: bool = True):
         eng = self.model._engine
@@ -80,6 +141,14 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 L.sumsq_live(g, table, self._ss, self._ss_ws)
             ss = self._ss
+        if not self._plain():  # parameter groups: ONE launch over the (live run, group) segments
+            self._sync_lr()
+            hyper = [(q["lr"], q["betas"][0], q["betas"][1], q["eps"], q["weight_decay"], q.get("decoupled_weight_decay", False))
+                     for q in self.param_groups]
+            L.adam_flat_groups(flat, g, self._m, self._v, self._segment_table(eng), hyper, self._step, sumsq_t=ss,
+                               max_norm=clip_max_norm or 0.0, grad_scale=grad_scale)
+            eng.params_version += 1
+            return
         b1, b2 = grp["betas"]
         if table is None:
             L.adam_flat(flat, g, self._m, self._v, grp["lr"], b1, b2, grp["eps"], grp["weight_decay"], self._step, sumsq_t=ss,
@@ -99,7 +168,7 @@ class FusedAdam(torch.optim.Optimizer):
     # model.parameters() order; its moments are the slice of the flat m / v buffers at that parameter's offset.
     def _slices(self, eng):
         by_id = {id(eng.named[n]): (eng.offsets[n], eng.named[n].numel(), tuple(eng.named[n].shape), n) for n in eng.order}
-        return [by_id[id(p)] for p in self.param_groups[0]["params"]]
+        return [by_id[id(p)] for g in self.param_groups for p in g["params"]]  # (the indices run through the groups in order)
 
     def state_dict(self):
         eng = self.model.engine()
@@ -111,9 +180,10 @@ class FusedAdam(torch.optim.Optimizer):
                 state[i] = {"step": torch.tensor(float(self._step)), "exp_avg": self._m[o:o + k].view(shape).clone(),
                             "exp_avg_sq": self._v[o:o + k].view(shape).clone()}
         groups = []
-        for g in self.param_groups:
+        index = PG.index_lists([g["params"] for g in self.param_groups])
+        for g, idx in zip(self.param_groups, index):
             d = {k: v for k, v in g.items() if k != "params"}
-            d["params"] = list(range(len(g["params"])))
+            d["params"] = idx
             groups.append(d)
         return {"state": state, "param_groups": groups}
 
@@ -124,6 +194,12 @@ class FusedAdam(torch.optim.Optimizer):
         v = torch.zeros_like(flat)
         self._ever = set()
         if "state" in sd:  # torch.optim.Adam schema (reference-written or ours)
+            if len(self.param_groups) > 1 or len(sd["param_groups"]) > 1:  # several groups: the same index lists, as torch asks
+                mine = PG.index_lists([g["params"] for g in self.param_groups])
+                theirs = [[int(i) for i in g["params"]] for g in sd["param_groups"]]
+                if mine != theirs:
+                    raise ValueError("loaded state dict has other parameter groups than the optimizer: "
+                                     f"{[len(t) for t in theirs]} parameters per group against {[len(t) for t in mine]}")
             sl = self._slices(eng)
             steps = set()
             for i, st in sd["state"].items():
