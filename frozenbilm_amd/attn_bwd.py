@@ -227,6 +227,8 @@ def pos_table_grads_batched(eng, run, pc: PosChain):
             L.attn_pos_grad(neg, X, Y, dlo, dcnt, cmax, d[nf:], B, pc.S, Sp, nh, rcnt, klen=pc.klen, row0=pc.row0)
         # [e, h, r, 64] fp32 -> [e, r, h*64 + .] bf16, into this table's column block
         L.heads_to_rows_bf16(d, dpb[:, :, col0:col0 + H])
+    if getattr(run, "lora_pos_wait", False):  # LoRA on query_proj / key_proj: their weights' gradient through PQ / PK
+        eng._lora_pos_bwd(run, pc, dpb)
     tmp = torch.empty(E, rcnt, H, dtype=F32, device=dev)
     L.gemm(dpb, eng.WposT_exec[:E], out_f32=tmp)
     dR = L.zeros(span2, H, dtype=F32, device=dev)

@@ -122,6 +122,16 @@ class AdapterSite:
     downT: Optional[torch.Tensor] = None      # after every refresh (_adapter_bwd_operands)
 
 
+@dataclass
+class LoraSite:
+    """LoRA on one frozen projection of one layer: W' = W + s.B.A lives in the rows [t*H, (t+1)*H) of that layer's packed Wqkv
+    (and the matching columns of WqkvT); lora_A.weight is the `down` and lora_B.weight the `up` of its gradient products."""
+    name: str   # the module: deberta.encoder.layer.<li>.attention.self.<query|key|value>_proj
+    li: int
+    t: int      # 0 query, 1 key, 2 value
+    idx: int    # its place in the compose table and in the backward operand packs
+
+
 class Engine(LiveSetMixin):
     def __init__(self, model):
         self.m = model
@@ -162,6 +172,7 @@ class Engine(LiveSetMixin):
         self._build_flat()
         self._pack_frozen()
         self._build_trainable_operands()
+        self._build_lora()
         self._compose_ev = None  # (event after layer 0, event after everything) of the last compose (refresh_trainable_operands)
         self._relidx: Dict[int, torch.Tensor] = {}
         self._pos_cache: Dict[int, torch.Tensor] = {}  # per-layer position projections of inference forwards (_pos_proj_cached)
@@ -376,6 +387,134 @@ class Engine(LiveSetMixin):
             wv = self.Pb["deberta.embeddings.linear_video.weight"]
             self.Wv = wv if self.Fp == self.F else torch.zeros(H, self.Fp, dtype=BF16, device=dev)
 
+    def _build_lora(self):
+        """The LoRA sites (model.lora_rank > 0): the table of the compose launch (include/fbl_lora.h) over the fp32 masters, the
+        LoRA parameters in the flat buffer and the packed operands, all of which never move."""
+        from .model.deberta import LORA_TARGETS
+
+        m, H = self.m, self.H
+        self.lora_r = int(getattr(m, "lora_rank", 0) or 0)
+        self.lora_sites: Dict[tuple, LoraSite] = {}
+        self.lora_composes = 0   # compose launches so far (tests: inside weights_frozen() two forwards compose once)
+        self._lora_ops = None    # backward operands (_lora_bwd_operands), dropped by every refresh
+        self._lora_idx = None
+        self._lora_names = set()
+        self._lora_pos = False
+        if not self.lora_r:
+            return
+        self.lora_s = float(m.lora_scale)
+        recs = []
+        for i in range(self.nL):
+            for tname in m.lora_targets:
+                t = LORA_TARGETS.index(tname)
+                nm = f"deberta.encoder.layer.{i}.attention.self.{tname}"
+                self.lora_sites[(i, t)] = LoraSite(name=nm, li=i, t=t, idx=len(recs))
+                recs.append(dict(W=self.P[nm + ".weight"], A=self.P[nm + ".lora_A.weight"], B=self.P[nm + ".lora_B.weight"],
+                                 scale=self.lora_s, dst=self.Lw[i]["Wqkv"][t * H:(t + 1) * H],
+                                 dstT=self.Lw[i]["WqkvT"][:, t * H:(t + 1) * H]))
+        self._lora_recs = recs
+        self._lora_table = L.LoraTable(recs, self.dev)
+        self._lora_names = {s.name for s in self.lora_sites.values()}
+        self._lora_pos = any(t < 2 for (_, t) in self.lora_sites)  # query / key: their weights also project the position table
+        self._lora_Aop = torch.zeros(len(recs), 64, H, dtype=BF16, device=self.dev)   # [A ; 0]: K-contiguous, r padded to 64
+        self._lora_BTop = torch.zeros(len(recs), 64, H, dtype=BF16, device=self.dev)  # [B^T ; 0]
+
+    def _compose_lora(self):
+        """W' = W + s.B.A of every LoRA site into the packed bf16 operands, one launch on the current stream; then the
+        [Wq ; Wk]^T copies of the position-gradient chain follow the composed WqkvT."""
+        L.lora_compose(self._lora_table)
+        self.lora_composes += 1
+        if self._lora_pos:
+            H, nL = self.H, self.nL
+            for e, li in enumerate([nL - 1, nL - 1] + list(range(nL - 2, -1, -1)) + [nL - 1]):
+                self.WposT_exec[e].copy_(self.Lw[li]["WqkvT"][:, : 2 * H])
+
+    def merge_lora(self):
+        """W <- W + s.B.A in the fp32 masters (the compose kernel's fp32 result: the same arithmetic as the packed operands),
+        then B <- 0.  The caller drops this engine (model.merge_lora)."""
+        L.lora_compose(L.LoraTable([dict(r, dst32=r["W"]) for r in self._lora_recs], self.dev))
+        for r in self._lora_recs:
+            r["B"].zero_()
+        self.invalidate_operands()
+
+    def _lora_bwd_operands(self):
+        """[A ; 0] and [B^T ; 0] (bf16 [sites, 64, H]) of every LoRA site, gathered out of the flat bf16 parameter copy on first
+        use after a refresh: the K-contiguous operands of the two narrow GEMMs in front of the weight-gradient products."""
+        if self._lora_ops is None:
+            r, H, dev = self.lora_r, self.H, self.dev
+            if self._lora_idx is None:
+                i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+                sites = sorted(self.lora_sites.values(), key=lambda s: s.idx)
+                oA = i64([self.offsets[s.name + ".lora_A.weight"] for s in sites])
+                oB = i64([self.offsets[s.name + ".lora_B.weight"] for s in sites])
+                rowmajor = torch.arange(r * H, device=dev)
+                transposed = (torch.arange(H, device=dev)[None, :] * r + torch.arange(r, device=dev)[:, None]).reshape(-1)
+                self._lora_idx = ((oA[:, None] + rowmajor[None]).reshape(-1), (oB[:, None] + transposed[None]).reshape(-1))
+            ns = len(self.lora_sites)
+            self._lora_Aop[:, :r].copy_(self.flat_bf16.index_select(0, self._lora_idx[0]).view(ns, r, H))
+            self._lora_BTop[:, :r].copy_(self.flat_bf16.index_select(0, self._lora_idx[1]).view(ns, r, H))
+            self._lora_ops = (self._lora_Aop, self._lora_BTop)
+        return self._lora_ops
+
+    def _lora_products(self, site: LoraSite, dy, x):
+        """The operands of one execution's two weight-gradient products of a LoRA site, in the shape of an adapter's
+        (fbl_adapter_bwd_dw): dB += dy^T.u with u = s.x.A^T, dA += v^T.x with v = s.dy.B; u, v bf16 [rows, 64], zero beyond r."""
+        Aop, BTop = self._lora_bwd_operands()
+        n = dy.shape[0]
+        u = torch.empty(n, 64, dtype=BF16, device=self.dev)
+        v = torch.empty(n, 64, dtype=BF16, device=self.dev)
+        L.gemm(x, Aop[site.idx], alpha=self.lora_s, out_bf16=u)
+        L.gemm(dy, BTop[site.idx], alpha=self.lora_s, out_bf16=v)
+        return (dy, u, v, x)
+
+    def _lora_live(self, site: Optional[LoraSite]) -> bool:
+        return site is not None and any((site.name + k) in self.Gl for k in (".lora_A.weight", ".lora_B.weight"))
+
+    def _lora_bwd(self, run, li: int, t: int, dy, x):
+        """Park the weight-gradient products of LoRA site (li, t) for one layer execution: dy bf16 [N, H] the gradient of the
+        projection's output, x bf16 [N, H] its input.  A site without a live member launches nothing."""
+        site = self.lora_sites.get((li, t))
+        if not self._lora_live(site):
+            return
+        run.dw_pending.append((self.lora_r, site.name, self._lora_products(site, dy, x), run.dw_count, None))
+        run.dw_count += 1
+
+    def _dw_outputs(self, nm: str, Gl):
+        """(dWu, dWd, dbd) views of the flat gradient buffer behind the parked products of `nm` (None: dead, no output): an
+        adapter's up / down weights and down bias, or a LoRA site's lora_B (the `up`) and lora_A (the `down`)"""
+        if nm in getattr(self, "_lora_names", ()):
+            return Gl.get(nm + ".lora_B.weight"), Gl.get(nm + ".lora_A.weight"), None
+        return Gl.get(nm + ".up.weight"), Gl.get(nm + ".down.weight"), Gl.get(nm + ".down.bias")
+
+    def _lora_pos_bwd(self, run, pc, dpb):
+        """The position path of the LoRA'd query / key projections: PQ = query_proj(R_e), PK = key_proj(R_e) of every execution
+        e, R_e the normalised table behind that execution's position dropout.  dpb bf16 [E, rcnt, 2H] = [dPQ | dPK] of the
+        table rows rmin .. rmin + rcnt (the others have zero gradient).  Same two products as the token path, rows = rcnt."""
+        H, nL = self.H, self.nL
+        order = [nL - 1, nL - 1] + list(range(nL - 2, -1, -1)) + [nL - 1]  # the executions of the chain (WposT_exec)
+        segs: Dict[str, list] = {}
+        for e in range(dpb.shape[0]):
+            sites = [self.lora_sites.get((order[e], t)) for t in (0, 1)]
+            if not any(self._lora_live(s) for s in sites):
+                continue
+            if run.p_hid > 0:
+                xe = torch.empty(self.span2, H, dtype=BF16, device=self.dev)
+                L.dropout_f32(run.R32, run.p_hid, pc.seeds[e], out_bf16=xe)
+            else:
+                xe = run.Rb
+            x = xe[pc.rmin:pc.rmin + pc.rcnt]
+            for t, site in enumerate(sites):
+                if self._lora_live(site):
+                    segs.setdefault(site.name, []).append(self._lora_products(site, dpb[e][:, t * H:(t + 1) * H], x))
+        groups, nseg = [], 0
+        for nm, sg in list(segs.items()) + [(None, None)]:
+            if groups and (nm is None or len(groups) == L.ADW_MAX_ADAPTERS or nseg + len(sg) > L.ADW_MAX_SEGMENTS):
+                L.adapter_bwd_dw(groups, A=self.lora_r)
+                groups, nseg = [], 0
+            if nm is not None:
+                groups.append((sg, *self._dw_outputs(nm, self.Gl)))
+                nseg += len(sg)
+
     def relidx(self, S: int) -> torch.Tensor:
         if S not in self._relidx:
             v = rel_index_vector(S, self.cfg.position_buckets, self.cfg.max_rel, self.cfg.att_span)
@@ -429,6 +568,9 @@ class Engine(LiveSetMixin):
                 self._compose_ev = self._compose_adapter_down()
         if self.F and self.Fp != self.F:
             self.Wv[:, : self.F] = self.Pb["deberta.embeddings.linear_video.weight"]
+        if self.lora_r:  # W' = W + s.B.A into the packed Q/K/V operands (fp32 masters: does not wait for the cast above)
+            self._lora_ops = None
+            self._compose_lora()
 
     def _compose_adapter_down(self):
         """Rows [H, H+A) of the merged weights / biases: Wd.W and Wd.b + bd for every layer (see MergedPack), from the
@@ -565,7 +707,8 @@ class Engine(LiveSetMixin):
                                       "carry the attention dropout mask, which the fused kernel regenerates instead of storing)")
         # Decoder on the selected rows (opt-in `model.decoder_rows`): both enhanced-mask-decoder passes, the head and their
         # backward run on the labelled rows / the logit_rows only; calls that need every row keep the full decoder.
-        if (getattr(m, "decoder_rows", False) and not want_attn and not want_hidden and not self.eager_logits
+        # (a model with LoRA on its attention projections takes the full decoder: the selected-rows route is not checked with it)
+        if (getattr(m, "decoder_rows", False) and not self.lora_r and not want_attn and not want_hidden and not self.eager_logits
                 and (full_labels is not None or logit_rows is not None) and not torch.cuda.is_current_stream_capturing()):
             run.dec_grid = (rows_labelled if full_labels is not None else logit_rows.to(self.dev).long().view(-1))
         if pk is not None and full_labels is not None:  # the head works on packed rows; the labels are looked up on the grid
@@ -794,6 +937,8 @@ class Engine(LiveSetMixin):
             run.attn_out.append(probs)
         if run.save:
             sv.qkv, sv.pqk, sv.ctx, sv.lse = qkv[:N], qkv[N:, : 2 * H], ctx, lse  # (run.save: never the inference shortcuts)
+            if self.lora_r:  # the projections' bf16 inputs, kept for the LoRA weight-gradient products (N x H x 2 bytes each)
+                sv.xkv, sv.xq = kv.bf16, (q.bf16 if q is not None else None)
         return self._layer_tail(run, li, sv, ctx, q if q is not None else kv, N, tail=self.span2)
 
     def _layer_tail(self, run, li: int, sv: "LayerSave", ctx, resid: Stream, N: int, tail=0) -> Stream:
@@ -873,6 +1018,8 @@ class Engine(LiveSetMixin):
         # ---- relative-position table: R = LayerNorm_enc(rel_embeddings.weight)   (:474-478)
         r, _ = self._ln(run, "deberta.encoder.LayerNorm", y=self.rel_emb, resid=None, N=self.span2, want_f32=run.p_hid > 0)
         run.rel_norm, run.R32, Rb = r.norm, r.plain, r.bf16
+        if self._lora_pos and run.save:  # (only a model with LoRA on query / key keeps it beyond the forward: a rank-0 model's
+            run.Rb = Rb                  #  tensors live exactly as long as they always did)
         # ---- encoder (:507-575)
         hs: List[Stream] = [emb]
         x = emb
@@ -1250,8 +1397,7 @@ class Engine(LiveSetMixin):
             for (A, _rows), recs in take.items():
                 Gl = getattr(self, "Gl", None)  # the gradient views of the live leaves (before a live set exists: all of them)
                 Gl = self.G if Gl is None else Gl
-                L.adapter_bwd_dw([([seg], Gl.get(nm + ".up.weight"), Gl.get(nm + ".down.weight"), Gl.get(nm + ".down.bias"))
-                                  for nm, seg in recs], A=A)  # (a dead member of a live adapter: no output)
+                L.adapter_bwd_dw([([seg], *Engine._dw_outputs(self, nm, Gl)) for nm, seg in recs], A=A)  # (a dead member: no output)
             kept = {id(r) for r in rest}
             for rec in pend:  # [dy | dz | 0] operands whose last reader has now been enqueued go back to the pool (same stream)
                 if id(rec) not in kept and rec[4] is not None and tuple(rec[4].shape) == self._dyz_shape:
@@ -1264,8 +1410,9 @@ class Engine(LiveSetMixin):
             for key in run.dw_ready_keys:
                 if key in parked:
                     still.append(key)
-                else:
-                    red.ready(key)
+                elif not (getattr(run, "lora_pos_wait", False) and key.startswith("layer")):
+                    red.ready(key)  # (LoRA on query / key: the position chain at the end of backward still adds to the layers'
+                    #                  buckets; they leave with finish())
             run.dw_ready_keys[:] = still
 
     def _layer_bwd(self, run, sv: "LayerSave", dout: torch.Tensor):
@@ -1328,6 +1475,8 @@ class Engine(LiveSetMixin):
             self.reducer.window()
         if not sv.emd:
             dqkv = self._attn_bwd(run, sv, dctx)
+            for t in range(3 if self.lora_r else 0):
+                self._lora_bwd(run, li, t, dqkv[:, t * H:(t + 1) * H], sv.xkv)
             dx = torch.empty(N, H, dtype=F32, device=dev)
             L.gemm(dqkv, W["WqkvT"], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dx)
             return dx, None
@@ -1340,6 +1489,8 @@ class Engine(LiveSetMixin):
         else:
             dqkv = self._attn_bwd(run, sv, dctx)
             dq_op, dkv_op = dqkv[:, :H], dqkv[:, H:]
+            for t in range(3 if self.lora_r else 0):  # the query projection reads the query stream, key / value read hs[-2]
+                self._lora_bwd(run, li, t, dqkv[:, t * H:(t + 1) * H], sv.xq if t == 0 else sv.xkv)
         dq = torch.empty(N, H, dtype=F32, device=dev)
         L.gemm(dq_op, W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
         return dq, dkv_op
@@ -1521,7 +1672,8 @@ class Engine(LiveSetMixin):
             return end()
         # the position-table gradients feed only encoder.LayerNorm: dead, the whole chain (fbl_attn_pos_grad, the strided-batch
         # projection behind it) is not launched and the attention backward keeps nothing for it
-        if any(REL_LN + k in self.Gl for k in ("weight", "bias")):
+        run.lora_pos_wait = self._lora_pos and any(t < 2 and self._lora_live(s) for (_, t), s in self.lora_sites.items())
+        if any(REL_LN + k in self.Gl for k in ("weight", "bias")) or run.lora_pos_wait:
             run.pos_chain = pos_chain_buffers(self, run)
             if dec is not None:  # the two decoder executions are the first of the chain also when nothing was selected (R = 0:
                 # they were not saved; zero tables keep the chain's order equal to the order of WposT_exec)
@@ -1615,8 +1767,9 @@ class Engine(LiveSetMixin):
         if run.pos_chain is not None:
             dR = pos_table_grads_batched(self, run, run.pos_chain)
             run.pos_chain = None
-            L.ln_bwd(dR, rn.t, rn.stats, rn.gamma, dgamma=self.Gl.get("deberta.encoder.LayerNorm.weight"),
-                     dbeta=self.Gl.get("deberta.encoder.LayerNorm.bias"), ws=self._ln_ws)
+            if any(REL_LN + k in self.Gl for k in ("weight", "bias")):  # (the chain also runs for LoRA on query / key alone)
+                L.ln_bwd(dR, rn.t, rn.stats, rn.gamma, dgamma=self.Gl.get("deberta.encoder.LayerNorm.weight"),
+                         dbeta=self.Gl.get("deberta.encoder.LayerNorm.bias"), ws=self._ln_ws)
         if red:
             red.ready("relln")
         if dx is None:  # nothing live in the embedding stage and no input takes a gradient: the backward ends here
@@ -1735,6 +1888,10 @@ class LayerSave:
     psave: torch.Tensor = None
     msave: torch.Tensor = None
     # decoder on selected rows (_decoder_rows_fwd) in place of qkv; pqk, ctx and lse above are then those of its R compact rows
+    # LoRA (engine.lora_r > 0): the bf16 inputs of the projections -- the key/value stream (the layer input) and, in the decoder
+    # passes, the query stream
+    xkv: Optional[torch.Tensor] = None
+    xq: Optional[torch.Tensor] = None
     qc: Optional[torch.Tensor] = None   # bf16 [R, H]: the projected query of the selected rows
     kvp: Optional[torch.Tensor] = None  # bf16 [N, 2H]: K|V of hs[-2], shared by both passes; set = a decoder-rows execution
 
@@ -1778,6 +1935,7 @@ class Run:
     seed_emb: int = 0                              # dropout behind it
     rel_norm: NormRef = None                       # encoder.LayerNorm over the relative-position table
     R32: Optional[torch.Tensor] = None             # fp32 [2*span, H]: that table, materialised for its dropout (training)
+    Rb: Optional[torch.Tensor] = None              # bf16 [2*span, H]: the table as a GEMM operand, before any dropout
     # ---- layers
     layers: list = field(default_factory=list)     # LayerSave / BertLayerSave per execution that has a backward
     dec_grid: Optional[torch.Tensor] = None        # model.decoder_rows: the selected rows on the padded grid, caller's order
@@ -1814,6 +1972,7 @@ class Run:
     _pos_keep: list = field(default_factory=list)  # captured steps: tensors the side stream reads, referenced for the step's life
     pos_chain: Optional["PosChain"] = None         # attn_bwd.PosChain: what the position-table gradients collect per execution
     pos_extra: Optional[tuple] = None              # ... of the LayerSave.extra execution, which joins the chain last
+    lora_pos_wait: bool = False                    # LoRA on query / key is live: the chain adds to the layers' gradients at the end
     # ---- partial fine-tuning
     plan: Optional[object] = None                  # live_set.StagePlan: the stages whose backward runs (None: all of them)
     live_version: int = 0                          # the engine's live set this step was planned for

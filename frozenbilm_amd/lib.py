@@ -66,6 +66,7 @@ QROWS_SIGNATURES = _header_signatures("fbl_qrows.h")  # the enhanced mask decode
 LIVE_SIGNATURES = _header_signatures("fbl_live.h")    # clip norm and Adam over a live set of the flat trainable buffer
 PREDICT_SIGNATURES = _header_signatures("fbl_predict.h")  # top-k / label rank / NLL of selected rows from their logits
 GROUP_SIGNATURES = _header_signatures("fbl_groups.h")  # Adam over parameter groups of the flat trainable buffer
+LORA_SIGNATURES = _header_signatures("fbl_lora.h")    # LoRA merged into the packed bf16 operands: W' = W + s.B.A
 
 _LIB = None
 
@@ -82,7 +83,8 @@ def load(path: Optional[str] = None):
             "there is no CPU/eager fallback")
     lib = C.CDLL(p)
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
-                              *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items()):
+                              *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items(),
+                              *LORA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -856,6 +858,45 @@ def adam_flat_groups(p, g, m, v, table, groups, step, sumsq_t=None, max_norm=0.0
     _chk(load().fbl_adam_flat_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(table), len(hyper) // ADAM_GROUP_FLOATS, hyper,
                                      int(step), _p(sumsq_t), float(max_norm), float(grad_scale), _stream()),
          "fbl_adam_flat_groups")
+
+
+LORA_MAX_RANK, LORA_SITE_WORDS = 64, 16  # FBL_LORA_MAX_RANK / FBL_LORA_SITE_WORDS of include/fbl_lora.h
+
+
+class LoraTable:
+    """The site table of include/fbl_lora.h, twice: the host array fbl_lora_compose validates and the device copy its kernel
+    reads.  sites: dicts with W fp32 [O, I] (row-major view), A fp32 [r, I], B fp32 [O, r] (contiguous), scale, dst bf16 [O, I]
+    and dstT bf16 [I, O] (row-major views), optional dst32 fp32 [O, I].  The tensors are referenced for the table's life."""
+
+    def __init__(self, sites, device):
+        import struct
+
+        words, self.keep = [], []
+        for s in sites:
+            W, A, B, dst, dstT, d32 = s["W"], s["A"], s["B"], s["dst"], s["dstT"], s.get("dst32")
+            _req(W, torch.float32, "W"); _req(A, torch.float32, "A"); _req(B, torch.float32, "B")
+            _req(dst, torch.bfloat16, "dst"); _req(dstT, torch.bfloat16, "dstT")
+            O, I = W.shape
+            r = A.shape[0]
+            assert A.shape == (r, I) and B.shape == (O, r) and A.is_contiguous() and B.is_contiguous(), (W.shape, A.shape, B.shape)
+            assert tuple(dst.shape) == (O, I) and tuple(dstT.shape) == (I, O)
+            ld32 = 0
+            if d32 is not None:
+                _req(d32, torch.float32, "dst32")
+                assert tuple(d32.shape) == (O, I)
+                ld32 = _rows2d(d32, "dst32")
+            bits = struct.unpack("<I", struct.pack("<f", float(s["scale"])))[0]
+            words += [W.data_ptr(), _rows2d(W, "W"), A.data_ptr(), B.data_ptr(), dst.data_ptr(), _rows2d(dst, "dst"),
+                      dstT.data_ptr(), _rows2d(dstT, "dstT"), _p(d32) or 0, ld32, O, I, r, bits, 0, 0]
+            self.keep.append((W, A, B, dst, dstT, d32))
+        self.n = len(sites)
+        self.host = (C.c_int64 * max(len(words), 1))(*words)
+        self.dev = torch.tensor(words or [0], dtype=torch.int64, device=device)
+
+
+def lora_compose(table: LoraTable):
+    """dst = dstT^T = bf16(W + s.B.A) (and dst32 = the fp32 value) for every site of `table`: one launch"""
+    _chk(load().fbl_lora_compose(table.host, _p(table.dev), table.n, _stream()), "fbl_lora_compose")
 
 
 def cast_bf16(x, out):

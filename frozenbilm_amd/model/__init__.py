@@ -2,7 +2,7 @@
 from .adapter import Adapter
 from .bert import BertConfig, BertForMaskedLM
 from .config import DebertaV2Config
-from .deberta import DebertaV2ForMaskedLM, MaskedLMOutput
+from .deberta import LORA_DEFAULT_TARGETS, DebertaV2ForMaskedLM, MaskedLMOutput
 
 
 def build_model(args, config=None):
@@ -30,6 +30,9 @@ def build_model(args, config=None):
             ft_ln=getattr(args, "ft_ln", True),
             n_ans=getattr(args, "n_ans", 0),
             freeze_last=getattr(args, "freeze_last", True),
+            lora_rank=getattr(args, "lora_rank", 0),
+            lora_alpha=getattr(args, "lora_alpha", None),
+            lora_targets=getattr(args, "lora_targets", LORA_DEFAULT_TARGETS),
         )
     if "deberta" not in name:
         raise NotImplementedError(f"only the DeBERTa-v2 and BERT paths are implemented (model_name={name!r})")
@@ -46,6 +49,9 @@ def build_model(args, config=None):
         dropout=args.dropout,
         n_ans=getattr(args, "n_ans", 0),
         freeze_last=getattr(args, "freeze_last", True),
+        lora_rank=getattr(args, "lora_rank", 0),
+        lora_alpha=getattr(args, "lora_alpha", None),
+        lora_targets=getattr(args, "lora_targets", LORA_DEFAULT_TARGETS),
     )
 
 

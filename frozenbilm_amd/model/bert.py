@@ -93,8 +93,11 @@ def param_shapes(cfg: BertConfig, features_dim: int, n_ans: int):
 
 class BertForMaskedLM(nn.Module):
     def __init__(self, config, features_dim=768, max_feats=10, freeze_lm=True, ft_ln=True, freeze_mlm=True, n_ans=0,
-                 freeze_last=True):
+                 freeze_last=True, lora_rank=0, lora_alpha=None, lora_targets=("query_proj", "value_proj")):
         super().__init__()
+        if lora_rank:
+            raise NotImplementedError("LoRA on the frozen attention projections (lora_rank > 0) is implemented for the DeBERTa "
+                                      "model only")
         self.config = BertConfig.from_any(config)
         cfg = self.config
         self.features_dim, self.max_feats = features_dim, max_feats

@@ -157,6 +157,40 @@ def param_shapes(cfg: DebertaV2Config, features_dim: int, ds_attn: int, ds_ff: i
     return sh
 
 
+LORA_TARGETS = ("query_proj", "key_proj", "value_proj")  # the frozen projections a low-rank update may sit on
+LORA_DEFAULT_TARGETS = ("query_proj", "value_proj")
+LORA_MAX_RANK = 64  # FBL_LORA_MAX_RANK of include/fbl_lora.h
+
+
+def check_lora(rank, alpha, targets):
+    """(rank, scale s = alpha / rank, targets in the order of LORA_TARGETS) of the constructor arguments, or ValueError"""
+    if isinstance(rank, bool) or not isinstance(rank, int) or not 0 <= rank <= LORA_MAX_RANK:
+        raise ValueError(f"lora_rank must be an integer in 0..{LORA_MAX_RANK} (got {rank!r})")
+    if isinstance(targets, str):
+        targets = (targets,)
+    targets = tuple(targets)
+    unknown = [t for t in targets if t not in LORA_TARGETS]
+    if unknown:
+        raise ValueError(f"lora_targets must be a subset of {LORA_TARGETS} (got {unknown})")
+    if rank > 0 and not targets:
+        raise ValueError("lora_rank > 0 needs at least one of lora_targets " + str(LORA_TARGETS))
+    if rank == 0:
+        return 0, 0.0, ()
+    alpha = rank if alpha is None else alpha
+    return rank, float(alpha) / rank, tuple(t for t in LORA_TARGETS if t in targets)
+
+
+def lora_shapes(cfg: DebertaV2Config, rank: int, targets) -> "OrderedDict[str, tuple]":
+    """the LoRA parameters: per layer and target, lora_A.weight [r, H] and lora_B.weight [H, r]"""
+    sh: "OrderedDict[str, tuple]" = OrderedDict()
+    for i in range(cfg.num_hidden_layers if rank else 0):
+        for t in targets:
+            p = f"deberta.encoder.layer.{i}.attention.self.{t}"
+            sh[p + ".lora_A.weight"] = (rank, cfg.hidden_size)
+            sh[p + ".lora_B.weight"] = (cfg.hidden_size, rank)
+    return sh
+
+
 def flat_order(cfg: DebertaV2Config, names: List[str]) -> List[str]:
     """Trainable names in backward-completion order (bucket order of the gradient all-reduce)."""
     def take(prefix):
@@ -188,8 +222,14 @@ class DebertaV2ForMaskedLM(nn.Module):
         dropout=0.1,
         n_ans=0,
         freeze_last=True,
+        lora_rank=0,
+        lora_alpha=None,
+        lora_targets=LORA_DEFAULT_TARGETS,
     ):
         super().__init__()
+        # LoRA on the frozen Q/K/V projections (an extension): W' = W + (alpha / rank) . B . A is the module's weight wherever
+        # it is used; merged into the packed bf16 operands once per step (engine.Engine._compose_lora), no dropout
+        self.lora_rank, self.lora_scale, self.lora_targets = check_lora(lora_rank, lora_alpha, lora_targets)
         self.config = DebertaV2Config.from_any(config)
         self.config.validate_supported()
         cfg = self.config
@@ -223,6 +263,15 @@ class DebertaV2ForMaskedLM(nn.Module):
             if name.endswith("word_embeddings.weight"):
                 t[cfg.pad_token_id].zero_()  # :1089-1090
             self._register(name, nn.Parameter(t, requires_grad=self._trainable(name)))
+        # the LoRA parameters come from a generator of their own: every other parameter keeps its initial bits whatever the rank
+        g2 = torch.Generator().manual_seed(1)
+        for name, shape in lora_shapes(cfg, self.lora_rank, self.lora_targets).items():
+            if ".lora_A." in name:  # nn.Linear's reset_parameters: kaiming_uniform_(a=sqrt(5)) = U(-1/sqrt(fan_in), 1/sqrt(fan_in))
+                bound = 1.0 / shape[1] ** 0.5
+                t = (torch.rand(shape, generator=g2) * 2 - 1) * bound
+            else:
+                t = torch.zeros(shape)
+            self._register(name, nn.Parameter(t, requires_grad=True))
         emb = self._module("deberta.embeddings")
         emb.register_buffer("position_ids", torch.arange(cfg.max_position_embeddings).expand((1, -1)))
         self._engine = None
@@ -271,7 +320,7 @@ class DebertaV2ForMaskedLM(nn.Module):
     def _trainable(self, name: str) -> bool:
         if name.startswith("answer_"):
             return not self.freeze_last
-        if "linear_video" in name or "adapter" in name:
+        if "linear_video" in name or "adapter" in name or ".lora_" in name:
             return True
         return bool(self.ft_ln and "LayerNorm" in name)
 
@@ -337,6 +386,22 @@ class DebertaV2ForMaskedLM(nn.Module):
                     self._engine._ops_version = None
 
         return scope()
+
+    def lora_names(self) -> List[str]:
+        """the module names that carry a LoRA pair (`<name>.lora_A.weight`, `<name>.lora_B.weight`), layer by layer"""
+        return [f"deberta.encoder.layer.{i}.attention.self.{t}" for i in range(self.config.num_hidden_layers if self.lora_rank else 0)
+                for t in self.lora_targets]
+
+    @torch.no_grad()
+    def merge_lora(self):
+        """W <- W + s.B.A in the fp32 masters of every LoRA'd projection -- the compose kernel's own fp32 result, so the bf16
+        operands (hence the eval logits) keep their bits -- then B <- 0 and the engine is rebuilt on next use.  The state_dict
+        without its `lora_*` keys is then a plain reference checkpoint."""
+        if not self.lora_rank:
+            return self
+        self.engine().merge_lora()
+        self.invalidate()
+        return self
 
     def invalidate(self):
         """Drop the packed bf16 operands / flat buffers (after load_state_dict, .to(), set_answer_embeddings)."""
