@@ -4,6 +4,7 @@
 #include "../../include/fbl.h"
 #include "../../include/fbl_live.h"
 #include "../../include/fbl_groups.h"
+#include "../../include/fbl_ema.h"
 
 namespace {
 
@@ -946,6 +947,86 @@ __global__ __launch_bounds__(256) void adam_flat_groups_kernel(float* p, const f
     *(f32x4*)(p + at) = po;
   }
 }
+// ---- Adam over parameter groups WITH the moving average of the updated parameter (include/fbl_ema.h): a sibling of
+// adam_flat_groups_kernel, not a parameter of it -- that kernel keeps its code.  Table walk and Adam arithmetic are its, line
+// for line (tests/test_gpu_adam_ema.py holds the two together bit for bit); the average rides on the parameter while it is in
+// a register: one more 16-byte load and one more 16-byte store per four elements, nine streams instead of seven.
+__global__ __launch_bounds__(256) void adam_flat_groups_ema_kernel(float* p, const float* g, float* m, float* v, float* ema,
+                                                                   long n, const int64_t* tab, int ng, AdamGroupArgs a,
+                                                                   const float* sumsq, float max_norm, float grad_scale,
+                                                                   float ema_w) {
+  __shared__ GroupTab t;
+  __shared__ __attribute__((aligned(16))) float rec[FBL_ADAM_MAX_GROUPS * ADAM_REC];
+  long ns = tab[0];
+  ns = ns < 0 ? 0 : (ns > LIVE_MAX_RANGES ? LIVE_MAX_RANGES : ns);
+  for (int s = threadIdx.x; s < ns; s += blockDim.x) {
+    t.begin[s] = tab[2 + 3 * s];
+    t.cum[s] = tab[3 + 3 * s];
+    const long gs = tab[4 + 3 * s];
+    t.group[s] = (gs < 0 || gs >= ng) ? -1 : (int)gs;
+  }
+  for (int i = threadIdx.x; i < ng * ADAM_REC; i += blockDim.x) rec[i] = a.rec[i];
+  __syncthreads();
+  const long n_live = ns > 0 ? tab[1] : 0;
+  const int nr = (int)ns;
+  float clip = grad_scale;
+  if (sumsq && max_norm > 0.f) {
+    const float norm = sqrtf(sumsq[0]) * grad_scale;
+    clip *= fminf(1.0f, max_norm / (norm + 1e-6f));
+  }
+  for (long c = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; c < n_live; c += (long)gridDim.x * blockDim.x * 4) {
+    int lo = 0, hi = nr;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (t.cum[mid] <= c) lo = mid; else hi = mid;
+    }
+    const long at = t.begin[lo] + (c - t.cum[lo]);
+    const int grp = t.group[lo];
+    if (at < 0 || at + 4 > n || (at & 3) || grp < 0) continue;  // (a malformed table, a group out of range: nothing is touched)
+    const f32x4 h0 = *(const f32x4*)(rec + grp * ADAM_REC), h1 = *(const f32x4*)(rec + grp * ADAM_REC + 4);
+    const float lr = h0[0], b1 = h0[1], b2 = h0[2], eps = h0[3], wd = h1[0], bc1 = h1[2], bc2 = h1[3];
+    const bool decoupled = h1[1] != 0.f;
+    const f32x4 gv = *(const f32x4*)(g + at), pv = *(const f32x4*)(p + at);
+    const f32x4 mv = *(const f32x4*)(m + at), vv = *(const f32x4*)(v + at);
+    const f32x4 ev = *(const f32x4*)(ema + at);
+    f32x4 po, mo, vo, eo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      // adam_flat_groups_kernel's arithmetic, instruction for instruction (contraction off, the one fma written out); then the
+      // average in lerp form, a rounded difference and one fma: where the average equals the new parameter, d is +0 and the
+      // average keeps its bits.
+#pragma clang fp contract(off)
+      float gi = gv[e] * clip;
+      float pi = pv[e];
+      if (decoupled) pi = pi * (1.f - lr * wd);
+      else if (wd != 0.f) gi = gi + wd * pi;
+      const float mi = b1 * mv[e] + (1.f - b1) * gi;
+      const float vi = b2 * vv[e] + ((1.f - b2) * gi) * gi;
+      mo[e] = mi;
+      vo[e] = vi;
+      const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+      po[e] = __builtin_fmaf(-(lr / bc1), mi / denom, pi);
+      const float d = po[e] - ev[e];
+      eo[e] = __builtin_fmaf(ema_w, d, ev[e]);
+    }
+    *(f32x4*)(m + at) = mo;
+    *(f32x4*)(v + at) = vo;
+    *(f32x4*)(p + at) = po;
+    *(f32x4*)(ema + at) = eo;
+  }
+}
+// a <-> b, fp32 [n], n % 8 == 0 (so n / 4 whole 16-byte words): the words move as bits (uint32x4: NaN payloads and signed
+// zeros travel untouched); every word is read and written by one lane only, both loads before both stores
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* a, float* b, long n4) {
+  u32x4* a4 = (u32x4*)a;
+  u32x4* b4 = (u32x4*)b;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const u32x4 x = a4[i], y = b4[i];
+    a4[i] = y;
+    b4[i] = x;
+  }
+}
 __global__ void cast_bf16_kernel(const float* in, bf16* out, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = f2bf(in[i]);
 }
@@ -1326,6 +1407,37 @@ extern "C" int fbl_adam_flat_groups(float* p, const float* g, float* m, float* v
   }
   hipLaunchKernelGGL(adam_flat_groups_kernel, dim3(grid1d(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
                      (long)n, segs, n_groups, a, sumsq, max_norm, grad_scale);
+  FBL_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- include/fbl_ema.h
+extern "C" int fbl_adam_flat_groups_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const int64_t* segs,
+                                        int n_groups, const float* hyper, int step, const float* sumsq, float max_norm,
+                                        float grad_scale, float ema_w, void* stream) {
+  if (!p || !g || !m || !v || !ema || !segs || !hyper || n_groups < 1 || n_groups > FBL_ADAM_MAX_GROUPS) return FBL_ERR_ARG;
+  if (!(ema_w > 0.f && ema_w <= 1.f)) return FBL_ERR_ARG;  // (a NaN weight too)
+  if ((n & 7) || !live_aligned(p) || !live_aligned(g) || !live_aligned(m) || !live_aligned(v) || !live_aligned(ema))
+    return FBL_ERR_ALIGN;
+  if (n <= 0) return 0;
+  AdamGroupArgs a{};
+  for (int k = 0; k < n_groups; ++k) {
+    const float* h = hyper + k * FBL_ADAM_GROUP_FLOATS;
+    float* r = a.rec + k * ADAM_REC;
+    for (int j = 0; j < FBL_ADAM_GROUP_FLOATS; ++j) r[j] = h[j];
+    r[6] = 1.0f - powf(h[1], (float)step);  // bc1, bc2: as fbl_adam_flat_groups forms them
+    r[7] = 1.0f - powf(h[2], (float)step);
+  }
+  hipLaunchKernelGGL(adam_flat_groups_ema_kernel, dim3(grid1d(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, p, g, m,
+                     v, ema, (long)n, segs, n_groups, a, sumsq, max_norm, grad_scale, ema_w);
+  FBL_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int fbl_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  if (!a || !b || a == b) return FBL_ERR_ARG;
+  if ((n & 7) || !live_aligned(a) || !live_aligned(b)) return FBL_ERR_ALIGN;
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(grid1d(n / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, a, b, (long)(n / 4));
   FBL_CHECK_LAUNCH();
   return 0;
 }

@@ -67,6 +67,7 @@ LIVE_SIGNATURES = _header_signatures("fbl_live.h")    # clip norm and Adam over 
 PREDICT_SIGNATURES = _header_signatures("fbl_predict.h")  # top-k / label rank / NLL of selected rows from their logits
 GROUP_SIGNATURES = _header_signatures("fbl_groups.h")  # Adam over parameter groups of the flat trainable buffer
 LORA_SIGNATURES = _header_signatures("fbl_lora.h")    # LoRA merged into the packed bf16 operands: W' = W + s.B.A
+EMA_SIGNATURES = _header_signatures("fbl_ema.h")      # the moving average of the trainable weights inside the Adam launch
 
 _LIB = None
 
@@ -84,7 +85,7 @@ def load(path: Optional[str] = None):
     lib = C.CDLL(p)
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
                               *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items(),
-                              *LORA_SIGNATURES.items()):
+                              *LORA_SIGNATURES.items(), *EMA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -858,6 +859,42 @@ def adam_flat_groups(p, g, m, v, table, groups, step, sumsq_t=None, max_norm=0.0
     _chk(load().fbl_adam_flat_groups(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(table), len(hyper) // ADAM_GROUP_FLOATS, hyper,
                                      int(step), _p(sumsq_t), float(max_norm), float(grad_scale), _stream()),
          "fbl_adam_flat_groups")
+
+
+def _flat32(t, n, name):
+    """a contiguous fp32 buffer of n elements, n % 8 == 0, 16-byte aligned: what the 16-byte accesses of include/fbl_ema.h need"""
+    _req(t, torch.float32, name)
+    if t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous buffer of {n} elements is needed, got {tuple(t.shape)}")
+    if n % 8 or t.data_ptr() % 16:
+        raise ValueError(f"{name}: {n} elements at {t.data_ptr():#x}: a multiple of 8 elements on a 16-byte boundary is needed")
+
+
+def adam_flat_groups_ema(p, g, m, v, ema, table, groups, step, ema_w, sumsq_t=None, max_norm=0.0, grad_scale=1.0):
+    """adam_flat_groups plus one step of the moving average `ema` of the updated parameter, ema += ema_w * (p_new - ema), in the
+    same launch (include/fbl_ema.h); 0 < ema_w <= 1."""
+    _req(table, torch.int64, "table")
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _flat32(t, p.numel(), name)
+    if ema.device != p.device:
+        raise ValueError(f"ema lives on {ema.device}, the parameters on {p.device}")
+    if not 0.0 < float(ema_w) <= 1.0:
+        raise ValueError(f"ema_w = {ema_w}: the weight of the new parameter lies in (0, 1]")
+    hyper = groups if isinstance(groups, C.Array) else adam_hyper(groups)
+    _chk(load().fbl_adam_flat_groups_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(table),
+                                         len(hyper) // ADAM_GROUP_FLOATS, hyper, int(step), _p(sumsq_t), float(max_norm),
+                                         float(grad_scale), float(ema_w), _stream()), "fbl_adam_flat_groups_ema")
+
+
+def swap_(a, b):
+    """a <-> b in place, bit for bit (fbl_swap_f32): two fp32 buffers of one size that do not overlap"""
+    _flat32(a, a.numel(), "a"); _flat32(b, a.numel(), "b")
+    if a.device != b.device:
+        raise ValueError(f"a lives on {a.device}, b on {b.device}")
+    lo, hi = sorted((a.data_ptr(), b.data_ptr()))
+    if a.numel() and lo + 4 * a.numel() > hi:
+        raise ValueError("swap_: the two buffers overlap")
+    _chk(load().fbl_swap_f32(_p(a), _p(b), a.numel(), _stream()), "fbl_swap_f32")
 
 
 LORA_MAX_RANK, LORA_SITE_WORDS = 64, 16  # FBL_LORA_MAX_RANK / FBL_LORA_SITE_WORDS of include/fbl_lora.h

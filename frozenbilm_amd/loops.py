@@ -10,6 +10,7 @@ from __future__ import annotations
 import contextlib
 import math
 import sys
+import warnings
 
 import torch
 
@@ -150,6 +151,27 @@ class LossLog:
 def frozen_weights(model):
     """`model.weights_frozen()` where the model has it (the MI355X model), a null context otherwise (test doubles)"""
     return model.weights_frozen() if hasattr(model, "weights_frozen") else contextlib.nullcontext()
+
+
+_EMA_WARNED = False
+
+
+def ema_weights(model, args):
+    """`model.ema_weights()` -- evaluate on the moving average of the trainable weights -- when ``args.eval_ema`` is set and the
+    model has an average (a `FusedAdam(..., ema_decay=)` attached to it that has stepped); a null context otherwise.  The option
+    without an average warns once per process and evaluates the raw weights."""
+    global _EMA_WARNED
+    if not getattr(args, "eval_ema", False):
+        return contextlib.nullcontext()
+    from .ema import attached
+
+    if attached(model) is None:
+        if not _EMA_WARNED:
+            _EMA_WARNED = True
+            warnings.warn("eval_ema is set but the model has no moving average (no FusedAdam(..., ema_decay=) attached to it has "
+                          "stepped): evaluating the raw weights")
+        return contextlib.nullcontext()
+    return model.ema_weights()
 
 
 def optimizer_step(loss, optimizer, model, max_norm, reducer=None, check=None):

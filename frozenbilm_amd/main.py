@@ -11,7 +11,7 @@ import contextlib
 
 import torch
 
-from .loops import EpochRunner, LossLog, frozen_weights, logged_step, tokenize, video_inputs
+from .loops import EpochRunner, LossLog, ema_weights, frozen_weights, logged_step, tokenize, video_inputs
 from .util.misc import mask_tokens
 
 
@@ -82,7 +82,7 @@ def evaluate(model, tokenizer, data_loader, device, args):
         model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, "Val:")
     log = LossLog(run, "mlm_loss", stop_on_nonfinite=False, delayed=True)  # (nothing to protect: read one batch late)
-    with frozen_weights(model), _mlm_accuracy(model, args) as acc:
+    with ema_weights(model, args), frozen_weights(model), _mlm_accuracy(model, args) as acc:  # (eval_ema: on the average)
         for _, batch_dict in run:
             out = model(**_prepare(batch_dict, tokenizer, device, args))
             if acc:

@@ -11,7 +11,7 @@ from functools import reduce
 import torch
 import torch.nn.functional as F
 
-from .loops import EpochRunner, LossLog, frozen_weights, logged_step, tokenize, video_inputs
+from .loops import EpochRunner, LossLog, ema_weights, frozen_weights, logged_step, tokenize, video_inputs
 from .util import dist
 from .videoqa import answer_logits
 
@@ -97,7 +97,8 @@ def evaluate(model, tokenizer, data_loader, device, dataset_name, args, split="t
         model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, f"{split}:")
     res = {}
-    with frozen_weights(model):  # nothing writes to the parameters during an evaluation: packed operands are reused
+    # nothing writes to the parameters during an evaluation: packed operands are reused (eval_ema: those of the moving average)
+    with ema_weights(model, args), frozen_weights(model):
         for _, batch_dict in run:
             scores = candidate_scores(model, tokenizer, batch_dict, device, args)
             preds = scores.round().long().squeeze(1) if scores.shape[1] == 1 else scores.max(1).indices

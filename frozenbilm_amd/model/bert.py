@@ -151,6 +151,7 @@ class BertForMaskedLM(nn.Module):
     get_param = DebertaV2ForMaskedLM.get_param
     device = DebertaV2ForMaskedLM.device
     weights_frozen = DebertaV2ForMaskedLM.weights_frozen
+    ema_weights = DebertaV2ForMaskedLM.ema_weights
     invalidate = DebertaV2ForMaskedLM.invalidate
     dropout_seed_base = DebertaV2ForMaskedLM.dropout_seed_base
 
@@ -163,6 +164,9 @@ class BertForMaskedLM(nn.Module):
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
+        from ..ema import refuse_if_open
+
+        refuse_if_open(self, "load_state_dict()")
         self.invalidate()
         # the reference's state dict also holds the tied decoder (cls.predictions.decoder.{weight,bias})
         sd = {k: v for k, v in state_dict.items() if not k.startswith("cls.predictions.decoder.")}

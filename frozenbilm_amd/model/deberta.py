@@ -387,6 +387,15 @@ class DebertaV2ForMaskedLM(nn.Module):
 
         return scope()
 
+    def ema_weights(self):
+        """Context manager: inside it the trainable parameters are the moving average kept by the attached
+        `FusedAdam(..., ema_decay=)` (frozenbilm_amd/ema.py; optim.FusedAdam.ema_weights) -- evaluate, export or save the
+        averaged model there; leaving restores every bit.  RuntimeError when no optimizer with an average is attached.  While it
+        is open `merge_lora()` and `load_state_dict()` are refused: what they write could not be swapped back."""
+        from ..ema import weights
+
+        return weights(self)
+
     def lora_names(self) -> List[str]:
         """the module names that carry a LoRA pair (`<name>.lora_A.weight`, `<name>.lora_B.weight`), layer by layer"""
         return [f"deberta.encoder.layer.{i}.attention.self.{t}" for i in range(self.config.num_hidden_layers if self.lora_rank else 0)
@@ -397,6 +406,9 @@ class DebertaV2ForMaskedLM(nn.Module):
         """W <- W + s.B.A in the fp32 masters of every LoRA'd projection -- the compose kernel's own fp32 result, so the bf16
         operands (hence the eval logits) keep their bits -- then B <- 0 and the engine is rebuilt on next use.  The state_dict
         without its `lora_*` keys is then a plain reference checkpoint."""
+        from ..ema import refuse_if_open
+
+        refuse_if_open(self, "merge_lora()")
         if not self.lora_rank:
             return self
         self.engine().merge_lora()
@@ -416,6 +428,9 @@ class DebertaV2ForMaskedLM(nn.Module):
         return super()._load_from_state_dict(*a, **k)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
+        from ..ema import refuse_if_open
+
+        refuse_if_open(self, "load_state_dict()")
         self.invalidate()
         # tolerate the reference-only keys (untied decoder copy, buffers)
         sd = {k: v for k, v in state_dict.items() if "lm_head.decoder" not in k}

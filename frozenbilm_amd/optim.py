@@ -35,13 +35,44 @@ ONE step counter, ONE clip norm over the live elements of all groups, a dead par
 With one group and coupled decay the step is the path described above, launch for launch; otherwise it is the norm (fbl_sumsq or
 fbl_sumsq_live) plus ONE fbl_adam_flat_groups (include/fbl_groups.h) over a device table of (live run, group) segments, cached per
 live set.  Checkpoints speak torch's multi-group schema: the parameter indices run through the groups in order.
+
+Moving average.  ``ema_decay=d`` (0 < d < 1; None, the default, is off: the launches, the exported state and the bits above) keeps
+an exponential moving average of the trainable weights, one fp32 buffer with the layout of ``engine.flat``.  It starts as a copy of
+the whole flat buffer in front of the first ``step()`` that finds none, and update number u (1-based, ``ema_updates``) moves it by
+``ema += w_u * (p_new - ema)`` with ``w_u = ema_weight(d, u, ema_warmup)``: ``1 - d``, or with ``ema_warmup`` ``1 - min(d, (1 + u) /
+(10 + u))`` (timm's and TensorFlow's rule).  The step is then the norm plus ONE fbl_adam_flat_groups_ema (include/fbl_ema.h) over
+the segment table, whatever the groups and the live set are -- a single coupled all-live group is one segment -- and p, m, v are
+those of the same optimizer without EMA, bit for bit.  The average moves where Adam moves: a dead parameter's average keeps its
+bits like its value and moments, so a parameter frozen after it trained keeps the average it had when it was frozen (it does NOT
+go on converging to the frozen value); a step with nothing live does not advance ``ema_updates``.  ``ema_state_dict()`` exports
+the averaged model (name -> fp32 tensor, every trainable-by-construction name: ``load_state_dict(sd, strict=False)`` on a fresh
+model), ``ema_weights()`` (also ``model.ema_weights()``) is a context inside which the model computes with the average: one
+fbl_swap_f32 of the flat buffer and the average on entry and one on exit, exact, with the engine's operands rebuilt both times.
+Inside it ``step()``, ``state_dict()``, ``load_state_dict()`` and a nested ``ema_weights()`` raise RuntimeError.  ``state_dict()``
+gains one top-level key, ``"fbl_ema": {"decay", "warmup", "updates", "params": {i: tensor}}`` (i as in ``"state"``, over all
+trainable-by-construction parameters); torch.optim.Adam reads ``state`` and ``param_groups`` only, so the file still loads there.
+Loading: with EMA on the key is restored (absent: the average starts at the next step from the then-current parameters); with EMA
+off it is ignored.
 """
 from __future__ import annotations
 
+import contextlib
+from collections import OrderedDict
+
 import torch
 
+from . import ema as EMA
 from . import lib as L
 from . import param_groups as PG
+
+
+def ema_weight(d: float, u: int, warmup: bool = False) -> float:
+    """The weight of the new parameters in update number `u` (1-based) of a moving average with decay `d`: 1 - d, or with
+    `warmup` 1 - min(d, (1 + u) / (10 + u)) -- the average follows the parameters closely at first (timm's ModelEmaV2 /
+    tf.train.ExponentialMovingAverage with num_updates).  Python floats; the launch takes it as fp32."""
+    if u < 1:
+        raise ValueError(f"update number {u}: the first update is number 1")
+    return 1.0 - (min(d, (1.0 + u) / (10.0 + u)) if warmup else d)
 
 
 def layerwise_param_groups(model, decay: float, no_decay=("LayerNorm", "bias")):
@@ -52,7 +83,12 @@ def layerwise_param_groups(model, decay: float, no_decay=("LayerNorm", "bias")):
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.0, *, param_groups=None,
-                 decoupled_weight_decay=False):
+                 decoupled_weight_decay=False, ema_decay=None, ema_warmup=False):
+        if ema_decay is not None and (isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float))
+                                      or not 0.0 < ema_decay < 1.0):
+            raise ValueError(f"ema_decay = {ema_decay!r}: None (off) or a float with 0 < ema_decay < 1")
+        if not isinstance(ema_warmup, bool):
+            raise ValueError(f"ema_warmup = {ema_warmup!r}: True or False")
         self.model = model
         names = model.trainable_names()
         cons = set(names)
@@ -75,6 +111,29 @@ class FusedAdam(torch.optim.Optimizer):
         self._ss = None
         self._ss_ws = None
         self._seg_tables = {}  # "engine" -> the engine the tables belong to; (device, live_version) -> table of include/fbl_groups.h
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = ema_warmup
+        self.ema_updates = 0   # updates the average has seen (u of ema_weight)
+        self._ema = None       # the average: fp32, the layout of engine.flat; inside ema_weights() it holds the raw parameters
+        self.ema_open = False  # inside ema_weights()
+        if self.ema_decay is not None:
+            EMA.attach(model, self)
+
+    @property
+    def has_ema(self) -> bool:
+        return self.ema_decay is not None and self._ema is not None
+
+    def _refuse_if_open(self, what):
+        if self.ema_open:
+            raise RuntimeError(f"FusedAdam.{what} inside ema_weights(): the flat buffer holds the moving average until the "
+                               "context is left")
+
+    def _ema_follow(self, flat):
+        """the average follows the model across devices like the moments, with the same error"""
+        if self._ema.numel() != flat.numel():
+            raise RuntimeError("the trainable set changed size under a live optimizer state")
+        if self._ema.device != flat.device:
+            self._ema = self._ema.to(flat.device)
 
     def _sync_lr(self):
         """a group with lr_scale follows group 0: its `lr` is what the next step uses"""
@@ -112,6 +171,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None, clip_max_norm: float = 0.0, grad_scale: float = 1.0):
+        self._refuse_if_open("step()")
         eng = self.model.engine()
         flat, g = eng.flat, eng.flat_grad
         if self._m is None:
@@ -126,6 +186,11 @@ class FusedAdam(torch.optim.Optimizer):
             self._ss = torch.zeros(1, dtype=torch.float32, device=flat.device)
             self._ss_ws = torch.empty(L.load().fbl_sumsq_ws_floats(), dtype=torch.float32, device=flat.device)
         grp = self.param_groups[0]
+        if self.ema_decay is not None:
+            if self._ema is None:  # the average starts from the parameters in front of this step's update
+                self._ema = flat.clone()
+            else:
+                self._ema_follow(flat)
         if not eng.live_any:  # nothing trains: nothing moves, the step does not count
             return
         table = None if eng.all_live else eng.live_table()  # (device ranges of the live set; None: the whole buffer)
@@ -141,6 +206,16 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 L.sumsq_live(g, table, self._ss, self._ss_ws)
             ss = self._ss
+        if self.ema_decay is not None:  # ONE launch whatever the groups and the live set are: Adam and the average
+            self._sync_lr()
+            hyper = [(q["lr"], q["betas"][0], q["betas"][1], q["eps"], q["weight_decay"], q.get("decoupled_weight_decay", False))
+                     for q in self.param_groups]
+            self.ema_updates += 1
+            L.adam_flat_groups_ema(flat, g, self._m, self._v, self._ema, self._segment_table(eng), hyper, self._step,
+                                   ema_weight(self.ema_decay, self.ema_updates, self.ema_warmup), sumsq_t=ss,
+                                   max_norm=clip_max_norm or 0.0, grad_scale=grad_scale)
+            eng.params_version += 1
+            return
         if not self._plain():  # parameter groups: ONE launch over the (live run, group) segments
             self._sync_lr()
             hyper = [(q["lr"], q["betas"][0], q["betas"][1], q["eps"], q["weight_decay"], q.get("decoupled_weight_decay", False))
@@ -170,7 +245,51 @@ class FusedAdam(torch.optim.Optimizer):
         by_id = {id(eng.named[n]): (eng.offsets[n], eng.named[n].numel(), tuple(eng.named[n].shape), n) for n in eng.order}
         return [by_id[id(p)] for g in self.param_groups for p in g["params"]]  # (the indices run through the groups in order)
 
+    # ---- the moving average: export, view, checkpoint
+    def ema_state_dict(self):
+        """name -> fp32 clone of the average in the parameter's shape, for every trainable-by-construction name:
+        `fresh_model.load_state_dict(sd, strict=False)` gives the averaged model"""
+        if not self.has_ema:
+            raise RuntimeError("ema_state_dict(): no average yet (ema_decay is off, or no step has run)")
+        eng = self.model.engine()
+        self._ema_follow(eng.flat)
+        avg = eng.flat if self.ema_open else self._ema  # (inside ema_weights() the two have changed places)
+        out = OrderedDict()
+        for n in self.model.trainable_names():
+            o, p = eng.offsets[n], eng.named[n]
+            out[n] = avg[o:o + p.numel()].view(p.shape).clone()
+        return out
+
+    @torch.no_grad()
+    def _ema_swap(self):
+        eng = self.model.engine()
+        self._ema_follow(eng.flat)
+        L.swap_(eng.flat, self._ema)
+        eng.invalidate_operands()  # (bumps params_version: packed operands, composed rows and cached projections are rebuilt)
+
+    def ema_weights(self):
+        """Context manager: inside it the model's trainable parameters ARE the average (one exchange of the flat buffer and the
+        average on entry, one on exit -- exact, so leaving restores every bit).  Evaluate, export or save the model inside it;
+        step(), state_dict(), load_state_dict() and a nested ema_weights() raise RuntimeError there."""
+        self._refuse_if_open("ema_weights()")
+        if not self.has_ema:
+            raise RuntimeError("ema_weights(): no average yet (ema_decay is off, or no step has run)")
+
+        @contextlib.contextmanager
+        def scope():
+            self._refuse_if_open("ema_weights()")
+            self._ema_swap()
+            self.ema_open = True
+            try:
+                yield self.model
+            finally:
+                self.ema_open = False
+                self._ema_swap()
+
+        return scope()
+
     def state_dict(self):
+        self._refuse_if_open("state_dict()")
         eng = self.model.engine()
         state = {}
         if self._m is not None and self._step > 0:
@@ -185,9 +304,36 @@ class FusedAdam(torch.optim.Optimizer):
             d = {k: v for k, v in g.items() if k != "params"}
             d["params"] = idx
             groups.append(d)
-        return {"state": state, "param_groups": groups}
+        out = {"state": state, "param_groups": groups}
+        if self.has_ema:
+            self._ema_follow(eng.flat)
+            out["fbl_ema"] = {"decay": self.ema_decay, "warmup": self.ema_warmup, "updates": self.ema_updates,
+                              "params": {i: self._ema[o:o + k].view(shape).clone()
+                                         for i, (o, k, shape, _) in enumerate(self._slices(eng))}}
+        return out
+
+    def _load_ema(self, sd, eng):
+        """EMA on and the key present: the average and its update count are restored (decay and warm-up stay the constructor's:
+        the file records them for the reader); absent: the average starts at the next step; EMA off: the key is ignored"""
+        if self.ema_decay is None:
+            return
+        self._ema, self.ema_updates = None, 0
+        rec = sd.get("fbl_ema")
+        if rec is None:
+            return
+        sl = self._slices(eng)
+        if sorted(int(i) for i in rec["params"]) != list(range(len(sl))):
+            raise ValueError(f"fbl_ema holds {len(rec['params'])} averaged parameters, the optimizer has {len(sl)}")
+        avg = eng.flat.clone()  # (the padding words between the parameters: those of the flat buffer)
+        for i, t in rec["params"].items():
+            o, k, shape, _ = sl[int(i)]
+            if tuple(t.shape) != shape:
+                raise ValueError(f"fbl_ema parameter {i}: {tuple(t.shape)} does not match parameter {shape}")
+            avg[o:o + k].copy_(t.reshape(-1).to(avg.device, avg.dtype))
+        self._ema, self.ema_updates = avg, int(rec["updates"])
 
     def load_state_dict(self, sd):
+        self._refuse_if_open("load_state_dict()")
         eng = self.model.engine()
         flat = eng.flat
         m = torch.zeros_like(flat)
@@ -229,3 +375,4 @@ class FusedAdam(torch.optim.Optimizer):
         self._ss = torch.zeros(1, dtype=torch.float32, device=flat.device)
         for g, s_ in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v_ for k, v_ in s_.items() if k != "params"})
+        self._load_ema(sd, eng)

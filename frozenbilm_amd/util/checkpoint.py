@@ -10,21 +10,28 @@ import torch
 from . import dist
 
 
-def checkpoint_dict(model, optimizer, epoch, args, trainable_only: bool = False):
-    sd = model.state_dict()
+def checkpoint_dict(model, optimizer, epoch, args, trainable_only: bool = False, ema_weights: bool = False):
+    """ema_weights: the "model" entry holds the moving average of the trainable weights (`model.ema_weights()`, kept by the
+    FusedAdam attached to the model) where the default holds the raw ones; the optimizer entry is the raw trajectory with its
+    `fbl_ema` key either way, taken outside that context."""
+    opt_sd = optimizer.state_dict() if optimizer is not None else None
+    if ema_weights:
+        with model.ema_weights():
+            sd = {k: v.clone() for k, v in model.state_dict().items()}  # (state_dict() hands out views of the live buffers)
+    else:
+        sd = model.state_dict()
     if trainable_only:
         keep = {n for n, p in model.named_parameters() if p.requires_grad}
         sd = {k: v for k, v in sd.items() if k in keep}
-    ck = {"model": sd, "optimizer": optimizer.state_dict() if optimizer is not None else None, "epoch": epoch,
-          "args": args}
+    ck = {"model": sd, "optimizer": opt_sd, "epoch": epoch, "args": args}
     if hasattr(model, "step_seed"):  # position of the dropout stream (an extra key: the reference's loader ignores it)
         ck["fbl"] = {"step_seed": int(model.step_seed)}
     return ck
 
 
-def save_checkpoint(model, optimizer, epoch, args, path, trainable_only: bool = False):
+def save_checkpoint(model, optimizer, epoch, args, path, trainable_only: bool = False, ema_weights: bool = False):
     """main.py:290-300 (``dist.save_on_master``)."""
-    dist.save_on_master(checkpoint_dict(model, optimizer, epoch, args, trainable_only), path)
+    dist.save_on_master(checkpoint_dict(model, optimizer, epoch, args, trainable_only, ema_weights), path)
 
 
 def load_checkpoint(model, path, optimizer=None, resume: bool = False, map_location="cpu"):

@@ -11,7 +11,7 @@ from functools import reduce
 import torch
 import torch.nn.functional as F
 
-from .loops import EpochRunner, LossLog, frozen_weights, logged_step, tokenize, video_inputs
+from .loops import EpochRunner, LossLog, ema_weights, frozen_weights, logged_step, tokenize, video_inputs
 from .util import dist
 
 
@@ -105,7 +105,8 @@ def evaluate(model, tokenizer, data_loader, device, dataset_name, args, threshol
         model.decoder_rows = True  # the enhanced mask decoder on the selected rows only
     run = EpochRunner(data_loader, args, f"{split}:")
     res = {}
-    with frozen_weights(model):  # nothing writes to the parameters during an evaluation: packed operands are reused
+    # nothing writes to the parameters during an evaluation: packed operands are reused (eval_ema: those of the moving average)
+    with ema_weights(model, args), frozen_weights(model):
         for _, batch_dict in run:
             video, video_mask = video_inputs(batch_dict, device)
             encoded = tokenize(tokenizer, batch_dict["text"], args)
