@@ -21,6 +21,7 @@ from . import lib as L
 from .predict import check_topk, of_call as predictions_of_call
 from .live_set import REL_LN, LiveSetMixin, flat_layout, stage_plan
 from .attn_bwd import ATTN_SCALE, _relidx_range, disent_attn_bwd, pos_chain_buffers, pos_table_grads_batched
+from .model.deberta import PROMPT_NAME
 from .model.relpos import rel_index_vector
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -169,6 +170,7 @@ class Engine(LiveSetMixin):
         self.attn_save_p = bool(o.get("attn_save_p", True))
         #   dw_group       adapter gradient products per launch (<= 16)
         self.dw_group = max(1, min(L.ADW_MAX_ADAPTERS, int(o.get("dw_group", 16))))
+        self.n_prompt = int(getattr(model, "n_prompt", 0))  # prompt tuning: trainable embedding rows in front of the text
         self._build_flat()
         self._pack_frozen()
         self._build_trainable_operands()
@@ -657,22 +659,26 @@ class Engine(LiveSetMixin):
         # nothing live and no input with a gradient: the call keeps no bookkeeping, as under no_grad (dropout stays live)
         need_grad = grad_on and (self.update_live() or bool(grad_in))
         T = video.shape[1] if use_video else 0
-        S = T + Lt
+        Pn = self.n_prompt  # prompt tuning: the sequence is [video T | prompt Pn | text Lt]; the text starts at T + Pn
+        S = T + Pn + Lt
         if S > self.cfg.max_position_embeddings:
             raise RuntimeError(
-                f"sequence of {S} positions (video {T} + text {Lt}) exceeds max_position_embeddings="
-                f"{self.cfg.max_position_embeddings} (the reference fails the same way, model/deberta.py:1020-1021,1392)")
+                f"sequence of {S} positions (video {T} + " + (f"prompt {Pn} + " if Pn else "") + f"text {Lt}) exceeds "
+                f"max_position_embeddings={self.cfg.max_position_embeddings} (the reference fails the same way, "
+                "model/deberta.py:1020-1021,1392)")
+        front = []
         if use_video:
             if video_mask is None:
                 video_mask = torch.ones(video.shape[:2], device=self.dev, dtype=attention_mask.dtype)
-            mask = torch.cat([video_mask.to(attention_mask.dtype), attention_mask], 1)
-        else:
-            mask = attention_mask
+            front.append(video_mask.to(attention_mask.dtype))
+        if Pn:  # prompt slots: mask 1, label -100
+            front.append(torch.ones(B, Pn, device=self.dev, dtype=attention_mask.dtype))
+        mask = torch.cat([*front, attention_mask], 1) if front else attention_mask
         mask = mask.to(torch.int32).contiguous()
         full_labels = None
         if labels is not None:
-            if use_video:
-                full_labels = torch.cat([torch.full((B, T), -100, dtype=torch.long, device=self.dev), labels], 1)
+            if T + Pn:
+                full_labels = torch.cat([torch.full((B, T + Pn), -100, dtype=torch.long, device=self.dev), labels], 1)
             else:
                 full_labels = labels
             full_labels = full_labels.contiguous().view(-1)
@@ -697,7 +703,7 @@ class Engine(LiveSetMixin):
         # mask stream.  Eager launches add the two on the host (Run.next_seed); a captured launch sequence keeps the per-site
         # constants as kernel arguments and reads the position from a device word (train_graph.py; include/fbl.h "Dropout
         # seeds") -- the same sum, so eager and replayed steps draw identical masks.
-        run = Run(B=B, S=S, T=T, Lt=Lt, train=train, save=need_grad, seed_base=self.seed_word_value() if train else 0,
+        run = Run(B=B, S=S, T=T, P=Pn, Lt=Lt, train=train, save=need_grad, seed_base=self.seed_word_value() if train else 0,
                   p_hid=self.cfg.hidden_dropout_prob if train else 0.0,
                   p_att=self.cfg.attention_probs_dropout_prob if train else 0.0,
                   p_ad=m.adapter_dropout if train else 0.0, mask=mask.view(-1), pk=pk, N=pk.n if pk is not None else B * S,
@@ -978,7 +984,7 @@ class Engine(LiveSetMixin):
 
     def _forward(self, run, input_ids, video, use_ans, want_hidden):
         cfg, H, dev = self.cfg, self.H, self.dev
-        B, S, T, Lt = run.B, run.S, run.T, run.Lt
+        B, S, T, Lt, Pn = run.B, run.S, run.T, run.Lt, run.P
         pk = run.pk
         N = run.N
         run.mask_i32 = run.mask  # [B*S]: the attention kernels index the mask on the padded grid
@@ -998,7 +1004,12 @@ class Engine(LiveSetMixin):
             L.gemm(vb, self.Wv, bias=self.P["deberta.embeddings.linear_video.bias"], out_f32=vproj)
             run.video_bf16 = vb
         t0 = torch.empty(B * S, H, dtype=F32, device=dev)
-        if run.embeds is None:
+        if Pn:  # [video | prompt | text]: the prompt rows straight from the fp32 master (no packed copy, nothing to refresh)
+            L.embed_assemble(input_ids if run.embeds is None else None, self.E32, vproj, self.P[PROMPT_NAME], T, Lt,
+                             t0.view(B, S, H))
+            if run.embeds is not None:
+                t0.view(B, S, H)[:, T + Pn:].copy_(run.embeds.detach())
+        elif run.embeds is None:
             L.embed_gather(input_ids, self.E32, vproj, T, t0)
         else:  # inputs_embeds in place of the gathered table rows (fp32, like them); the video slots in front as the gather puts them
             g0 = t0.view(B, S, H)
@@ -1802,6 +1813,10 @@ class Engine(LiveSetMixin):
                 L.gemm(dvT, vT, aux=gvw, aux_kind=L.AUX_ADD_F32, out_f32=gvw, N=self.F)
             if gvb is not None:
                 L.colsum(dv, gvb, self._cs_ws)
+        gp = self.Gl.get(PROMPT_NAME)
+        if gp is not None:  # prompt tuning, the prompt live: its gradient = the prompt slots' rows of dt0 summed over the batch in
+            # ascending b (fbl_prompt_grad: ordered fp32 adds onto what the buffer holds, reproducible bit for bit)
+            L.prompt_grad(dt0, None if pk is None else pk.row0, B, S, T, gp)
         if red:
             red.ready("emb")
             red.finish()
@@ -1825,7 +1840,7 @@ class Engine(LiveSetMixin):
                 grid = dt0
             else:  # positions without a row: exactly zero
                 grid = L.zeros(B * S, H, dtype=F32, device=dev).index_copy_(0, pk.sel, dt0)
-            gin["embeds"] = grid.view(B, S, H)[:, T:].to(run.embeds.dtype).contiguous()
+            gin["embeds"] = grid.view(B, S, H)[:, T + run.P:].to(run.embeds.dtype).contiguous()
         return gin
 
     def _conv_bwd(self, run, dout):
@@ -1920,6 +1935,7 @@ class Run:
     pk: Optional["Packing"] = None                 # packed-row layout of this pass (model.packed_rows) or None: the padded [B, S] grid
     N: int = 0                                     # activation rows: B*S, or pk.n
     embeds: Optional[torch.Tensor] = None          # inputs_embeds [B, L, H] given in place of input_ids
+    P: int = 0                                     # prompt slots between the video slots and the text (S = T + P + Lt)
     grad_in: tuple = ()                            # inputs that take a gradient of their own, as _StepFn lists them: "video", "embeds"
     hid_grad: bool = False                         # the hidden states handed out are differentiable (outputs of the step's node)
     video_dtype: Optional[torch.dtype] = None      # the caller's dtype of `video` (its gradient is returned in it)

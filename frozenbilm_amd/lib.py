@@ -68,6 +68,7 @@ PREDICT_SIGNATURES = _header_signatures("fbl_predict.h")  # top-k / label rank /
 GROUP_SIGNATURES = _header_signatures("fbl_groups.h")  # Adam over parameter groups of the flat trainable buffer
 LORA_SIGNATURES = _header_signatures("fbl_lora.h")    # LoRA merged into the packed bf16 operands: W' = W + s.B.A
 EMA_SIGNATURES = _header_signatures("fbl_ema.h")      # the moving average of the trainable weights inside the Adam launch
+PROMPT_SIGNATURES = _header_signatures("fbl_prompt.h")  # prompt tuning: the embedding rows with the prompt slots, its gradient
 
 _LIB = None
 
@@ -85,7 +86,7 @@ def load(path: Optional[str] = None):
     lib = C.CDLL(p)
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
                               *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items(),
-                              *LORA_SIGNATURES.items(), *EMA_SIGNATURES.items()):
+                              *LORA_SIGNATURES.items(), *EMA_SIGNATURES.items(), *PROMPT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -389,6 +390,39 @@ def embed_gather(ids, E, vproj, T, out_t):
         _req(vproj, torch.float32, "vproj")
         assert vproj.is_contiguous()
     _chk(load().fbl_embed_gather(_p(ids), _p(E), _p(vproj), B, T, L, H, _p(out_t), _stream()), "fbl_embed_gather")
+
+
+PROMPT_MAX = 128  # FBL_PROMPT_MAX of include/fbl_prompt.h
+
+
+def embed_assemble(ids, E, vproj, prompt, T, L, out_t):
+    """out_t [B, T + P + L, H] = [vproj | prompt | E[ids]] per sample (include/fbl_prompt.h); ids None: the text rows stay as
+    they are.  L: the text length (ids' when given)."""
+    P, H = prompt.shape
+    B = out_t.shape[0]
+    _req(prompt, torch.float32, "prompt"); _req(out_t, torch.float32, "out_t")
+    assert prompt.is_contiguous() and out_t.is_contiguous() and tuple(out_t.shape) == (B, T + P + L, H), (out_t.shape, T, P, L, H)
+    if ids is not None:
+        _req(ids, torch.int64, "ids"); _req(E, torch.float32, "E")
+        assert ids.is_contiguous() and E.is_contiguous() and tuple(ids.shape) == (B, L) and E.shape[1] == H
+    if vproj is not None:
+        _req(vproj, torch.float32, "vproj")
+        assert vproj.is_contiguous() and vproj.numel() == B * T * H
+    _chk(load().fbl_embed_assemble(_p(ids), _p(E) if ids is not None else None, _p(vproj), _p(prompt), B, T, P, L, H, _p(out_t),
+                                   _stream()), "fbl_embed_assemble")
+
+
+def prompt_grad(dt, row0, B, S, T, g):
+    """g [P, H] += sum over the samples, in ascending b, of dt[(row0[b] if row0 is given else b*S) + T + p] (include/fbl_prompt.h)"""
+    P, H = g.shape
+    _req(dt, torch.float32, "dt"); _req(g, torch.float32, "g")
+    assert dt.is_contiguous() and g.is_contiguous() and dt.dim() == 2 and dt.shape[1] == H
+    if row0 is not None:
+        _req(row0, torch.int32, "row0")
+        assert row0.is_contiguous() and row0.numel() >= B
+    else:
+        assert dt.shape[0] >= B * S
+    _chk(load().fbl_prompt_grad(_p(dt), _p(row0), B, S, T, P, H, _p(g), _stream()), "fbl_prompt_grad")
 
 
 def ln_fwd(*, y=None, p_drop=0.0, seed=0, r_plain=None, r_norm=None, gamma, beta, eps, rowmask=None, out_t=None,

@@ -33,6 +33,7 @@ def build_model(args, config=None):
             lora_rank=getattr(args, "lora_rank", 0),
             lora_alpha=getattr(args, "lora_alpha", None),
             lora_targets=getattr(args, "lora_targets", LORA_DEFAULT_TARGETS),
+            n_prompt=getattr(args, "n_prompt", 0),
         )
     if "deberta" not in name:
         raise NotImplementedError(f"only the DeBERTa-v2 and BERT paths are implemented (model_name={name!r})")
@@ -52,6 +53,7 @@ def build_model(args, config=None):
         lora_rank=getattr(args, "lora_rank", 0),
         lora_alpha=getattr(args, "lora_alpha", None),
         lora_targets=getattr(args, "lora_targets", LORA_DEFAULT_TARGETS),
+        n_prompt=getattr(args, "n_prompt", 0),
     )
 
 

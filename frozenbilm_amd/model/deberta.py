@@ -191,6 +191,17 @@ def lora_shapes(cfg: DebertaV2Config, rank: int, targets) -> "OrderedDict[str, t
     return sh
 
 
+PROMPT_MAX = 128  # FBL_PROMPT_MAX of include/fbl_prompt.h
+PROMPT_NAME = "deberta.embeddings.prompt_embeddings.weight"
+
+
+def check_n_prompt(n_prompt) -> int:
+    """the number of soft-prompt slots of the constructor argument, or ValueError"""
+    if isinstance(n_prompt, bool) or not isinstance(n_prompt, int) or not 0 <= n_prompt <= PROMPT_MAX:
+        raise ValueError(f"n_prompt must be an integer in 0..{PROMPT_MAX} (got {n_prompt!r})")
+    return n_prompt
+
+
 def flat_order(cfg: DebertaV2Config, names: List[str]) -> List[str]:
     """Trainable names in backward-completion order (bucket order of the gradient all-reduce)."""
     def take(prefix):
@@ -225,8 +236,12 @@ class DebertaV2ForMaskedLM(nn.Module):
         lora_rank=0,
         lora_alpha=None,
         lora_targets=LORA_DEFAULT_TARGETS,
+        n_prompt=0,
     ):
         super().__init__()
+        # prompt tuning (an extension): n_prompt trainable embedding rows between the video slots and the text of every sample
+        # (engine.Engine._forward assembles them with fbl_embed_assemble); 0 is the reference's sequence
+        self.n_prompt = check_n_prompt(n_prompt)
         # LoRA on the frozen Q/K/V projections (an extension): W' = W + (alpha / rank) . B . A is the module's weight wherever
         # it is used; merged into the packed bf16 operands once per step (engine.Engine._compose_lora), no dropout
         self.lora_rank, self.lora_scale, self.lora_targets = check_lora(lora_rank, lora_alpha, lora_targets)
@@ -272,6 +287,10 @@ class DebertaV2ForMaskedLM(nn.Module):
             else:
                 t = torch.zeros(shape)
             self._register(name, nn.Parameter(t, requires_grad=True))
+        if self.n_prompt:  # a generator of its own again: N(0, initializer_range), like the word embeddings it stands beside
+            g3 = torch.Generator().manual_seed(2)
+            t = torch.randn((self.n_prompt, cfg.hidden_size), generator=g3) * cfg.initializer_range
+            self._register(PROMPT_NAME, nn.Parameter(t, requires_grad=True))
         emb = self._module("deberta.embeddings")
         emb.register_buffer("position_ids", torch.arange(cfg.max_position_embeddings).expand((1, -1)))
         self._engine = None
@@ -320,7 +339,7 @@ class DebertaV2ForMaskedLM(nn.Module):
     def _trainable(self, name: str) -> bool:
         if name.startswith("answer_"):
             return not self.freeze_last
-        if "linear_video" in name or "adapter" in name or ".lora_" in name:
+        if "linear_video" in name or "adapter" in name or ".lora_" in name or name == PROMPT_NAME:
             return True
         return bool(self.ft_ln and "LayerNorm" in name)
 
@@ -415,6 +434,21 @@ class DebertaV2ForMaskedLM(nn.Module):
         self.invalidate()
         return self
 
+    @torch.no_grad()
+    def init_prompt_from_ids(self, ids):
+        """Text initialisation of prompt tuning: prompt row p <- the word embedding of token ids[p] (LongTensor [n_prompt])."""
+        if not self.n_prompt:
+            raise RuntimeError("init_prompt_from_ids needs a model built with n_prompt > 0")
+        E = self.get_param("deberta.embeddings.word_embeddings.weight")
+        ids = torch.as_tensor(ids)
+        if ids.dtype != torch.long or tuple(ids.shape) != (self.n_prompt,):
+            raise ValueError(f"ids must be a LongTensor of shape [{self.n_prompt}] (got {ids.dtype} {tuple(ids.shape)})")
+        if int(ids.min()) < 0 or int(ids.max()) >= E.shape[0]:
+            raise ValueError(f"ids outside the vocabulary 0..{E.shape[0] - 1}")
+        self.get_param(PROMPT_NAME).data.copy_(E.data[ids.to(E.device)])
+        self.invalidate()
+        return self
+
     def invalidate(self):
         """Drop the packed bf16 operands / flat buffers (after load_state_dict, .to(), set_answer_embeddings)."""
         self._engine = None
@@ -484,7 +518,8 @@ class DebertaV2ForMaskedLM(nn.Module):
         logit_rows=None,
     ):
         """Reference signature (model/deberta.py:1414-1427) plus two keyword extensions: ``output_hidden_states`` and
-        ``logit_rows`` -- int tensor of flat row indices b*S + s into the [B, S] token grid (S = video slots + text): the
+        ``logit_rows`` -- int tensor of flat row indices b*S + s into the [B, S] token grid (S = video slots + prompt slots +
+        text; ``n_prompt`` trainable rows sit between the video and the text, with mask 1 and no label): the
         prediction head then runs on those rows only and ``logits`` is [len(logit_rows), V] (the downstream loops read one
         [MASK] row per sample: videoqa.py:66-69,164-168, mc.py:166-170).  Under autograd these logits are differentiable and
         the head's backward runs on the same rows; the indices must then be distinct and inside the grid (ValueError), and

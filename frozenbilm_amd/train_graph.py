@@ -111,9 +111,11 @@ def route_for(model, call: Call) -> Optional[Route]:
     graphs feed token ids into static buffers and carry no edge to an input (no inputs_embeds, no `video` that takes a
     gradient); they are shape-static and end at the loss or the requested rows (no packed_rows / decoder_rows, no hidden
     states or attentions, no predict_topk: the predictions are formed by the eager route).  A model with LoRA on its attention
-    projections (lora_rank > 0) is served eagerly: no graph route has been checked against it."""
+    projections (lora_rank > 0) is served eagerly: no graph route has been checked against it; so is a model with prompt slots
+    (n_prompt > 0): the graphs' static feeds know the [video | text] sequence only."""
     if (not call.ids or call.embeds or call.hidden_states or call.attentions or model.packed_rows or model.decoder_rows
-            or getattr(model, "predict_topk", 0) or (call.grad and call.video_grad) or getattr(model, "lora_rank", 0)):
+            or getattr(model, "predict_topk", 0) or (call.grad and call.video_grad) or getattr(model, "lora_rank", 0)
+            or getattr(model, "n_prompt", 0)):
         return None
     if not model.training and not call.grad:
         return INFERENCE if model.inference_graphs and call.rows is not None and not call.labels else None

@@ -15,16 +15,17 @@ from .loops import EpochRunner, LossLog, ema_weights, frozen_weights, logged_ste
 from .util import dist
 
 
-def mask_row_logits(output_logits, encoded_ids, tokenizer, args):
-    """videoqa.py:66-69,163-166: rows of the text part (after the `max_feats` visual slots) where the input is [MASK]."""
-    delay = args.max_feats if args.use_video else 0
+def mask_row_logits(output_logits, encoded_ids, tokenizer, args, n_prompt=0):
+    """videoqa.py:66-69,163-166: rows of the text part (after the `max_feats` visual slots and the model's `n_prompt` prompt
+    slots) where the input is [MASK]."""
+    delay = (args.max_feats if args.use_video else 0) + n_prompt
     ids = encoded_ids.to(output_logits.device)
     return output_logits[:, delay: ids.size(1) + delay][ids == tokenizer.mask_token_id]
 
 
-def mask_rows(encoded_ids, tokenizer, args, device):
-    """Flat indices b*S + s (S = max_feats + L) of the [MASK] tokens: the rows mask_row_logits reads."""
-    delay = args.max_feats if args.use_video else 0
+def mask_rows(encoded_ids, tokenizer, args, device, n_prompt=0):
+    """Flat indices b*S + s (S = max_feats + n_prompt + L) of the [MASK] tokens: the rows mask_row_logits reads."""
+    delay = (args.max_feats if args.use_video else 0) + n_prompt
     b, l = torch.nonzero(encoded_ids == tokenizer.mask_token_id, as_tuple=True)
     return (b * (encoded_ids.size(1) + delay) + delay + l).to(device)
 
@@ -38,10 +39,11 @@ def answer_logits(model, tokenizer, encoded_ids, args, **feed):
     rows_route = (not torch.is_grad_enabled() or getattr(args, "train_logit_rows", False)
                   or getattr(args, "packed_rows", False) or getattr(args, "decoder_rows", False)
                   or getattr(args, "finetune_graphs", False))
+    n_prompt = getattr(model, "n_prompt", 0)  # prompt tuning: the text starts behind the model's prompt slots
     if hasattr(model, "engine") and rows_route:
-        rows = mask_rows(encoded_ids, tokenizer, args, feed["input_ids"].device)
+        rows = mask_rows(encoded_ids, tokenizer, args, feed["input_ids"].device, n_prompt=n_prompt)
         return model(logit_rows=rows, **feed)["logits"]
-    return mask_row_logits(model(**feed)["logits"], encoded_ids, tokenizer, args)
+    return mask_row_logits(model(**feed)["logits"], encoded_ids, tokenizer, args, n_prompt=n_prompt)
 
 
 def vqa_loss(logits, answer_id, dataset_name):
