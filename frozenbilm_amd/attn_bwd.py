@@ -89,7 +89,7 @@ def disent_attn_bwd(eng, run, sv, dctx, dqkv, dpqk, defer_pos=False):
     # `sv` (B, S, p_att, mask_i32, klen / qkv, pqk, ctx, lse, seed_att): what only an engine step carries is optional here.
     klen, border = run.klen, getattr(run, "border", None)
     scale = ATTN_SCALE
-    pk_ = getattr(run, "pk", None)
+    pk_ = getattr(run, "cb", None) or getattr(run, "pk", None)  # (cb: the compact backward next to a padded forward, Run.cb)
     row0 = pk_.row0 if pk_ is not None else None  # packed-row layout of q / k / v / dO and of the dQ / dK / dV outputs
     saved_p = getattr(sv, "psave", None) is not None
 

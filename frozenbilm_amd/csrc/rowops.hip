@@ -5,6 +5,7 @@
 #include "../../include/fbl_live.h"
 #include "../../include/fbl_groups.h"
 #include "../../include/fbl_ema.h"
+#include "../../include/fbl_rows.h"
 
 namespace {
 
@@ -174,8 +175,14 @@ struct LnBwdArgs {
   const float* dout; const int32_t* rowmask; const float* t; const float* stats; const float* gamma;
   float p_drop; uint64_t seed; const uint64_t* seed_dev; float* out_dt; bf16* out_dy_bf16; float* out_dy_f32; float* ws; int N, H;
   long ld_dyb;  // row stride of out_dy_bf16 (elements)
+  // ROWS kernels (fbl_ln_bwd_rows): a.N padded rows are walked; inv[row] is the compact row of padded row `row` or -1.
+  // dout / out_dt / out_dy_bf16 / out_dy_f32 live on compact rows, t / stats / rowmask / out_dy_pad on padded rows.
+  const int32_t* inv; bf16* out_dy_pad;
 };
-template <int EPL>
+// ROWS = false is the kernel as it always was (inv / out_dy_pad are not read).  ROWS = true: the same walk over the PADDED
+// rows -- same row -> wave assignment, same partial sums in the same order -- but a row without a compact row issues no
+// loads and adds nothing (in the padded call it adds +-0 to partial sums that started at +0: the sums are the same bits).
+template <int EPL, bool ROWS = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   constexpr int VEC = (EPL % 4 == 0) ? 4 : ((EPL % 2 == 0) ? 2 : 1);
   constexpr int NIT = EPL / VEC;
@@ -191,6 +198,17 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   const float inv_keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f;
   const uint64_t seed = a.p_drop > 0.f ? fbl_seed(a.seed, a.seed_dev) : 0;
   for (int row = blockIdx.x * 4 + wave; row < a.N; row += gridDim.x * 4) {
+    long crow = row;  // the row of dout / out_dt / out_dy_*
+    if (ROWS) {
+      const int cr = a.inv[row];  // (wave-uniform: one row per wave)
+      if (cr < 0) {               // no compact row: zeros in the padded dy, nothing else
+        const float z[VEC] = {};
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) stb<VEC>(a.out_dy_pad + (long)row * H + (it * 64 + lane) * VEC, z);
+        continue;
+      }
+      crow = cr;
+    }
     const float mean = a.stats[2 * (long)row], rstd = a.stats[2 * (long)row + 1];
     const float om = a.rowmask ? (float)a.rowmask[row] : 1.0f;
     float g[EPL], xh[EPL];
@@ -199,7 +217,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
     for (int it = 0; it < NIT; ++it) {
       const int col = (it * 64 + lane) * VEC;
       float d[VEC], x[VEC];
-      ldf<VEC>(a.dout + (long)row * H + col, d);
+      ldf<VEC>(a.dout + crow * H + col, d);
       ldf<VEC>(a.t + (long)row * H + col, x);
 #pragma unroll
       for (int c = 0; c < VEC; ++c) {
@@ -227,9 +245,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
         if (a.p_drop > 0.f) dy[c] *= fbl_dropout_scale(seed, (uint64_t)row * H + col + c, thr, inv_keep);
         dys[e] += dy[c];
       }
-      if (a.out_dt) stf<VEC>(a.out_dt + (long)row * H + col, dt);
-      if (a.out_dy_bf16) stb<VEC>(a.out_dy_bf16 + (long)row * a.ld_dyb + col, dy);
-      if (a.out_dy_f32) stf<VEC>(a.out_dy_f32 + (long)row * H + col, dy);
+      if (a.out_dt) stf<VEC>(a.out_dt + crow * H + col, dt);
+      if (a.out_dy_bf16) stb<VEC>(a.out_dy_bf16 + crow * a.ld_dyb + col, dy);
+      if (a.out_dy_f32) stf<VEC>(a.out_dy_f32 + crow * H + col, dy);
+      if (ROWS) stb<VEC>(a.out_dy_pad + (long)row * H + col, dy);
     }
   }
   // the three column sums leave one after the other through the same [4][H] LDS tile (a third of the LDS of folding them
@@ -257,7 +276,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
 // > 256 registers at H = 1536 and therefore runs one wave per SIMD), so four waves per SIMD keep enough rows in flight to
 // cover the HBM latency.  The two halves of a row exchange their (sum g, sum g*xhat) partials through LDS: one barrier
 // per iteration, double-buffered.  Same arithmetic and the same deterministic ws / fold protocol as ln_bwd_kernel.
-template <int EPL>
+template <int EPL, bool ROWS = false>
 __global__ __launch_bounds__(256, 3) void ln_bwd2_kernel(LnBwdArgs a) {
   static_assert(EPL % 2 == 0, "two waves share a row");
   constexpr int EW = EPL / 2;  // elements per lane
@@ -280,32 +299,44 @@ __global__ __launch_bounds__(256, 3) void ln_bwd2_kernel(LnBwdArgs a) {
   int par = 0;
   for (int base = blockIdx.x * 2; base < a.N; base += gridDim.x * 2, par ^= 1) {
     const int row = base + slot;
-    const bool live = row < a.N;
+    bool live = row < a.N;
     const int rr = live ? row : a.N - 1;
-    const float mean = a.stats[2 * (long)rr], rstd = a.stats[2 * (long)rr + 1];
-    const float om = live ? (a.rowmask ? (float)a.rowmask[rr] : 1.0f) : 0.f;
-    float g[EW], xh[EW];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int col = c0 + (it * 64 + lane) * VEC;
-      float d[VEC], x[VEC];
-      ldf<VEC>(a.dout + (long)rr * H + col, d);
-      ldf<VEC>(a.t + (long)rr * H + col, x);
-#pragma unroll
-      for (int c = 0; c < VEC; ++c) {
-        const int e = it * VEC + c;
-        const float dd = d[c] * om;
-        xh[e] = (x[c] - mean) * rstd;
-        dg[e] += dd * xh[e];
-        db[e] += dd;
-        g[e] = dd * gam[e];
-        s1 += g[e];
-        s2 += g[e] * xh[e];
-      }
+    long crow = row;  // the row of dout / out_dt / out_dy_*
+    bool pad_zero = false;
+    if (ROWS) {       // (wave-uniform: a wave works on one row; the barrier below stays outside every branch)
+      const int cr = a.inv[rr];
+      pad_zero = live && cr < 0;  // a padded row without a compact row: no loads, zeros in the padded dy
+      live = live && cr >= 0;
+      crow = cr;
     }
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
+    float g[EW], xh[EW];
+    float s1 = 0.f, s2 = 0.f, rstd = 0.f;
+    if (!ROWS || live) {
+      const long lr = ROWS ? crow : (long)rr;  // (ROWS = false: the dead slot of the last iteration reads row N-1, weight 0)
+      const float mean = a.stats[2 * (long)rr];
+      rstd = a.stats[2 * (long)rr + 1];
+      const float om = live ? (a.rowmask ? (float)a.rowmask[rr] : 1.0f) : 0.f;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int col = c0 + (it * 64 + lane) * VEC;
+        float d[VEC], x[VEC];
+        ldf<VEC>(a.dout + lr * H + col, d);
+        ldf<VEC>(a.t + (long)rr * H + col, x);
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+          const int e = it * VEC + c;
+          const float dd = d[c] * om;
+          xh[e] = (x[c] - mean) * rstd;
+          dg[e] += dd * xh[e];
+          db[e] += dd;
+          g[e] = dd * gam[e];
+          s1 += g[e];
+          s2 += g[e] * xh[e];
+        }
+      }
+      s1 = wave_sum(s1);
+      s2 = wave_sum(s2);
+    }
     if (lane == 0) {
       xch[par][slot][half][0] = s1;
       xch[par][slot][half][1] = s2;
@@ -327,10 +358,15 @@ __global__ __launch_bounds__(256, 3) void ln_bwd2_kernel(LnBwdArgs a) {
           if (a.p_drop > 0.f) dy[c] *= fbl_dropout_scale(seed, (uint64_t)row * H + col + c, thr, inv_keep);
           dys[e] += dy[c];
         }
-        if (a.out_dt) stf<VEC>(a.out_dt + (long)row * H + col, dt);
-        if (a.out_dy_bf16) stb<VEC>(a.out_dy_bf16 + (long)row * a.ld_dyb + col, dy);
-        if (a.out_dy_f32) stf<VEC>(a.out_dy_f32 + (long)row * H + col, dy);
+        if (a.out_dt) stf<VEC>(a.out_dt + crow * H + col, dt);
+        if (a.out_dy_bf16) stb<VEC>(a.out_dy_bf16 + crow * a.ld_dyb + col, dy);
+        if (a.out_dy_f32) stf<VEC>(a.out_dy_f32 + crow * H + col, dy);
+        if (ROWS) stb<VEC>(a.out_dy_pad + (long)row * H + col, dy);
       }
+    } else if (ROWS && pad_zero) {
+      const float z[VEC] = {};
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) stb<VEC>(a.out_dy_pad + (long)row * H + c0 + (it * 64 + lane) * VEC, z);
     }
   }
 #pragma unroll
@@ -1175,6 +1211,42 @@ extern "C" int fbl_ln_materialize(const float* t, const float* stats, const floa
 }
 
 extern "C" int64_t fbl_ln_bwd_ws_floats(int H) { return (int64_t)LNB_BLOCKS * 3 * H; }
+// the launch of fbl_ln_bwd / fbl_ln_bwd_rows: a.N (padded) rows decide the grid and the fold, ROWS picks the instantiation
+template <bool ROWS>
+static int ln_bwd_launch(const LnBwdArgs& a, float* dgamma, float* dbeta, float* dysum, hipStream_t stream) {
+  const int N = a.N, H = a.H;
+  int nblk;
+  if ((H / 64) % 2 == 0) {  // two waves per row, two rows per block iteration
+    nblk = (N + 1) / 2;
+    if (nblk > LNB_BLOCKS) nblk = LNB_BLOCKS;
+    dim3 grid(nblk);
+    switch (H / 64) {
+      case 2: hipLaunchKernelGGL((ln_bwd2_kernel<2, ROWS>), grid, dim3(256), 0, stream, a); break;
+      case 4: hipLaunchKernelGGL((ln_bwd2_kernel<4, ROWS>), grid, dim3(256), 0, stream, a); break;
+      case 8: hipLaunchKernelGGL((ln_bwd2_kernel<8, ROWS>), grid, dim3(256), 0, stream, a); break;
+      case 12: hipLaunchKernelGGL((ln_bwd2_kernel<12, ROWS>), grid, dim3(256), 0, stream, a); break;
+      case 16: hipLaunchKernelGGL((ln_bwd2_kernel<16, ROWS>), grid, dim3(256), 0, stream, a); break;
+      case 24: hipLaunchKernelGGL((ln_bwd2_kernel<24, ROWS>), grid, dim3(256), 0, stream, a); break;
+      case 32: hipLaunchKernelGGL((ln_bwd2_kernel<32, ROWS>), grid, dim3(256), 0, stream, a); break;
+      default: return FBL_ERR_SHAPE;
+    }
+  } else {
+    nblk = (N + 3) / 4;
+    if (nblk > LNB_BLOCKS) nblk = LNB_BLOCKS;
+    dim3 grid(nblk);
+    switch (H / 64) {
+      case 1: hipLaunchKernelGGL((ln_bwd_kernel<1, ROWS>), grid, dim3(256), 0, stream, a); break;
+      default: return FBL_ERR_SHAPE;
+    }
+  }
+  FBL_CHECK_LAUNCH();
+  if (dgamma || dbeta || dysum) {
+    hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3((3 * H + 31) / 32), dim3(256), 0, stream, a.ws, nblk, H, dgamma, dbeta, dysum);
+    FBL_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
 extern "C" int fbl_ln_bwd(const float* dout, const int32_t* rowmask, const float* t, const float* stats,
                           const float* gamma, float p_drop, uint64_t seed, const uint64_t* seed_dev, float* out_dt, void* out_dy_bf16,
                           float* out_dy_f32, float* dgamma, float* dbeta, float* dysum, float* ws, int N, int H,
@@ -1183,35 +1255,23 @@ extern "C" int fbl_ln_bwd(const float* dout, const int32_t* rowmask, const float
   if (N <= 0) return 0;
   if (ld_dy_bf16 == 0) ld_dy_bf16 = H;
   if (ld_dy_bf16 < H || (ld_dy_bf16 % 8)) return FBL_ERR_ALIGN;
-  LnBwdArgs a{dout, rowmask, t, stats, gamma, p_drop, seed, seed_dev, out_dt, (bf16*)out_dy_bf16, out_dy_f32, ws, N, H, ld_dy_bf16};
-  int nblk;
-  if ((H / 64) % 2 == 0) {  // two waves per row, two rows per block iteration
-    nblk = (N + 1) / 2;
-    if (nblk > LNB_BLOCKS) nblk = LNB_BLOCKS;
-    dim3 grid(nblk);
-    switch (H / 64) {
-      case 2: hipLaunchKernelGGL(ln_bwd2_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      case 4: hipLaunchKernelGGL(ln_bwd2_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      case 8: hipLaunchKernelGGL(ln_bwd2_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      case 12: hipLaunchKernelGGL(ln_bwd2_kernel<12>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      case 16: hipLaunchKernelGGL(ln_bwd2_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      case 24: hipLaunchKernelGGL(ln_bwd2_kernel<24>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      case 32: hipLaunchKernelGGL(ln_bwd2_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-      default: return FBL_ERR_SHAPE;
-    }
-  } else {
-    nblk = (N + 3) / 4;
-    if (nblk > LNB_BLOCKS) nblk = LNB_BLOCKS;
-    dim3 grid(nblk);
-    FBL_EPL_DISPATCH(H, ln_bwd_kernel, grid, a, (hipStream_t)stream);
-  }
-  FBL_CHECK_LAUNCH();
-  if (dgamma || dbeta || dysum) {
-    hipLaunchKernelGGL(ln_bwd_fold_kernel, dim3((3 * H + 31) / 32), dim3(256), 0, (hipStream_t)stream, ws, nblk, H,
-                       dgamma, dbeta, dysum);
-    FBL_CHECK_LAUNCH();
-  }
-  return 0;
+  LnBwdArgs a{dout, rowmask, t, stats, gamma, p_drop, seed, seed_dev, out_dt, (bf16*)out_dy_bf16, out_dy_f32, ws, N, H, ld_dy_bf16,
+              nullptr, nullptr};
+  return ln_bwd_launch<false>(a, dgamma, dbeta, dysum, (hipStream_t)stream);
+}
+
+extern "C" int fbl_ln_bwd_rows(const float* dout, const int32_t* inv, const int32_t* rowmask, const float* t, const float* stats,
+                               const float* gamma, float p_drop, uint64_t seed, const uint64_t* seed_dev, float* out_dt,
+                               void* out_dy_bf16, int64_t ld_dy_bf16, void* out_dy_pad_bf16, float* dgamma, float* dbeta,
+                               float* dysum, float* ws, int N_pad, int H, void* stream) {
+  if (H % 64 || H > 2048) return FBL_ERR_SHAPE;
+  if (!dout || !inv || !t || !stats || !gamma || !ws || !out_dy_pad_bf16) return FBL_ERR_ARG;
+  if (N_pad <= 0) return 0;
+  if (ld_dy_bf16 == 0) ld_dy_bf16 = H;
+  if (ld_dy_bf16 < H || (ld_dy_bf16 % 8)) return FBL_ERR_ALIGN;
+  LnBwdArgs a{dout, rowmask, t, stats, gamma, p_drop, seed, seed_dev, out_dt, (bf16*)out_dy_bf16, nullptr, ws, N_pad, H, ld_dy_bf16,
+              inv, (bf16*)out_dy_pad_bf16};
+  return ln_bwd_launch<true>(a, dgamma, dbeta, dysum, (hipStream_t)stream);
 }
 
 extern "C" int fbl_im2col3(const void* x_bf16, void* out_bf16, int B, int S, int H, void* stream) {

@@ -11,6 +11,7 @@ on the fly, so the fp32 normalised tensor is never written to HBM, and ``t`` dou
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
@@ -82,6 +83,8 @@ class Packing:
     inv: torch.Tensor    # int64 [B*S]: packed row of each padded row, -1 where it has none
     pos: torch.Tensor    # int64 [Np]: position s of each packed row
     n: int               # Np
+    sel32: Optional[torch.Tensor] = None  # sel / inv as int32, as the row kernels of include/fbl_rows.h take them (the
+    inv32: Optional[torch.Tensor] = None  # backward's own layout only: Engine._backward_rows)
 
 
 @dataclass
@@ -182,6 +185,7 @@ class Engine(LiveSetMixin):
         self.reducer = None  # set by parallel.GradReducer for data-parallel training
         self._dyz_pool: Dict[tuple, list] = {}  # [N, K_fold] operands of the folded adapter backward with their padding zeroed once
         self._dyz_shape = None                   # ... of the current batch shape only
+        self._dyz_compact = None                 # ... of the compact backward: one buffer of the current row count (_layer_bwd_compact)
         self.params_version = 0  # bumped by FusedAdam.step (which updates the flat buffer through raw pointers)
         self._ops_version = None
         self.skip_dead_layer = True
@@ -685,6 +689,10 @@ class Engine(LiveSetMixin):
             # The labelled rows are a function of the INPUT only: find them before anything is queued, so the host
             # synchronisation inside nonzero() waits for the previous step at most, never for this forward.
             rows_labelled = torch.nonzero(full_labels != -100).view(-1)
+        # The backward's own row layout (_backward_rows): decided here, from the INPUT, and read back at the point where the
+        # host already waits for the label rows -- the forward below does not use it.
+        bwd_rows = self._backward_rows(m, need_grad, tuple(k for k, _ in grad_in), mask, full_labels, logit_rows, want_hidden, want_attn,
+                                        B, S, T)
         if logit_rows is not None:
             if full_labels is not None:
                 raise RuntimeError("logit_rows cannot be combined with labels (the loss of a labelled call lives on its own rows)")
@@ -707,7 +715,8 @@ class Engine(LiveSetMixin):
                   p_hid=self.cfg.hidden_dropout_prob if train else 0.0,
                   p_att=self.cfg.attention_probs_dropout_prob if train else 0.0,
                   p_ad=m.adapter_dropout if train else 0.0, mask=mask.view(-1), pk=pk, N=pk.n if pk is not None else B * S,
-                  want_attn=bool(want_attn), labels=full_labels, rows=rows_labelled if full_labels is not None else None)
+                  want_attn=bool(want_attn), labels=full_labels, rows=rows_labelled if full_labels is not None else None,
+                  bwd_rows=bwd_rows)
         if want_attn and train and run.p_att > 0:
             raise NotImplementedError("output_attentions=True is served in eval mode (the probabilities of a training forward "
                                       "carry the attention dropout mask, which the fused kernel regenerates instead of storing)")
@@ -762,6 +771,43 @@ class Engine(LiveSetMixin):
         elif full_labels is not None:
             res["loss"] = loss_t
         return res
+
+    # Share of dropped rows from which the compact backward is faster than the padded one: the smallest share of the sweep of
+    # tools/bench_compact_bwd.py from which on every point beats the padded leg by more than the sweep's run-to-run spread
+    # (profiles/compact_backward.json; the gain is a step where the big dX GEMMs lose a round of tiles).  Measured
+    # at the bench grid (B = 32, S = 266).
+    COMPACT_BWD_MIN_DROPPED = 0.37
+
+    def _backward_rows(self, m, need_grad, grad_in, mask, full_labels, logit_rows, want_hidden, want_attn, B, S, T) -> Optional[Packing]:
+        """THE rule of the compact backward: the row layout the backward of this step runs its row-wise work on,
+        or None = the padded grid, exactly the backward there always was.  The forward is the padded one either way; the
+        gradients are the same bits either way (tests/test_gpu_compact_backward.py), so the choice is by shape and state only.
+        Compact needs ALL of:
+          * a step that keeps gradient bookkeeping, with a labelled loss (the configuration that is tested: calls with
+            logit_rows, output_hidden_states -- a gradient handed in on a hidden state reaches the padding rows -- or
+            output_attentions stay padded; so does a backward that is handed a gradient on the logits, decided in _backward);
+          * no stream capture (a captured step cannot follow a row count that changes with the batch);
+          * none of the other row layouts: model.packed_rows, model.decoder_rows;
+          * no LoRA, no prompt slots, no gradient reducer, probabilities saved by the forward (engine option attn_save_p):
+            not covered by a test on this route, they stay padded;
+          * every stage of the backward runs (partial fine-tuning with a dead bottom stays padded: not tested here);
+          * a batch with rows to drop, and -- unless model.compact_backward is True -- a dropped share of at least
+            COMPACT_BWD_MIN_DROPPED.
+        model.compact_backward: None (default) = this rule, False = always padded (A/B runs), True = the rule without the
+        share threshold (tests)."""
+        force = getattr(m, "compact_backward", None)
+        if (force is False or not need_grad or full_labels is None or logit_rows is not None or want_hidden or want_attn
+                or torch.cuda.is_current_stream_capturing() or getattr(m, "packed_rows", False) or getattr(m, "decoder_rows", False)
+                or self.lora_r or self.n_prompt or self.reducer is not None or not self.attn_save_p):
+            return None
+        plan = self.plan(grad_in)
+        if plan is not None and plan.lowest != 0:
+            return None
+        pk = self._make_packing(mask, full_labels, None, B, S, T)
+        if pk is None or (force is not True and 1.0 - pk.n / (B * S) < self.COMPACT_BWD_MIN_DROPPED):
+            return None
+        pk.sel32, pk.inv32 = pk.sel.to(torch.int32), pk.inv.to(torch.int32)
+        return pk
 
     def _make_packing(self, mask, full_labels, logit_rows, B, S, T) -> Optional[Packing]:
         """Packing of this batch, or None when no row can be dropped (one host read of B lengths)."""
@@ -1316,11 +1362,21 @@ class Engine(LiveSetMixin):
         return out
 
     # ------------------------------------------------------------------ backward
-    def _ln_bwd(self, name, dout, norm: NormRef, p_drop, seed, want_dy_bf16=True, dysum=None, tail=0, dy_out=None):
+    def _ln_bwd(self, name, dout, norm: NormRef, p_drop, seed, want_dy_bf16=True, dysum=None, tail=0, dy_out=None, cb=None):
         """dysum: optional [H] accumulator for colsum(dy) = the bias gradient of whatever produced y (adapter up.bias).
         tail > 0: dt is the first N rows of a [N+tail, H] buffer whose tail is zeroed (aux operand of the dX GEMM that
-        also produces the position-table gradient rows); the full buffer is returned as third value."""
+        also produces the position-table gradient rows); the full buffer is returned as third value.
+        cb: the compact backward (Run.cb) -- dout, dt and dy live on its rows, `norm` on the padded ones; the padded bf16 dy
+        (zero where a row has no compact row: what the adapter weight gradients read) is returned as third value."""
         N, H = dout.shape
+        if cb is not None:
+            dt = torch.empty(N, H, dtype=F32, device=self.dev)
+            dyb = dy_out if dy_out is not None else torch.empty(N, H, dtype=BF16, device=self.dev)
+            dy_pad = torch.empty(norm.t.shape[0], H, dtype=BF16, device=self.dev)
+            L.ln_bwd_rows(dout, cb.inv32, norm.t, norm.stats, norm.gamma, rowmask=norm.rowmask, p_drop=p_drop, seed=seed, out_dt=dt,
+                          out_dy_bf16=dyb, out_dy_pad=dy_pad, dgamma=self.Gl.get(name + ".weight"), dbeta=self.Gl.get(name + ".bias"),
+                          dysum=dysum, ws=self._ln_ws)
+            return dt, dyb, dy_pad
         dt_full = torch.empty(N + tail, H, dtype=F32, device=self.dev)
         dt = dt_full[:N]
         if tail:
@@ -1333,10 +1389,13 @@ class Engine(LiveSetMixin):
             return dt, dyb, dt_full
         return dt, dyb
 
-    def _adapter_bwd(self, run, site: AdapterSite, dyb, z, xin_b, seed, dz_out=None, pooled=None):
+    def _adapter_bwd(self, run, site: AdapterSite, dyb, z, xin_b, seed, dz_out=None, pooled=None, pad=None):
         """Backward of _adapter_fwd.  dyb: grad of the adapter output (bf16 [N,H]); returns grad of its input (bf16).
         dz_out: the caller folds dx = dy + dz.Wd into the next GEMM ([dy | dz] operand, _layer_bwd): dz is written there
-        (a column slice of that operand), no dx is formed and None is returned."""
+        (a column slice of that operand), no dx is formed and None is returned.
+        pad = (dy, z) on the padded rows, compact backward only (dyb and z are then on its rows, xin_b padded as ever): the
+        weight-gradient products keep the padded operands -- their reduction order over the rows is part of the result -- with
+        dz put back on the padded rows, zeros where a row has no compact row."""
         N, H = dyb.shape
         A, Ap = site.A, site.Ap
         dev = self.dev
@@ -1351,12 +1410,16 @@ class Engine(LiveSetMixin):
         if dz_out is None:
             dx = torch.empty(N, H, dtype=BF16, device=dev)
             L.gemm(dz, downT, aux=dyb, aux_kind=L.AUX_ADD_BF16, out_bf16=dx)
-        sk = max(2, min(16, N // 512))
         nm = site.name
         # the weight-gradient products of this adapter that feed a LIVE leaf (a dead one gets none: nothing is launched for it)
         gwu, gwd, gbd = (self.Gl.get(nm + k) for k in (".up.weight", ".down.weight", ".down.bias"))
         if gwu is None and gwd is None and gbd is None:
             return dx
+        if pad is not None:
+            dz_c, (dyb, z) = dz, pad
+            dz = torch.empty(dyb.shape[0], dz_c.shape[1], dtype=BF16, device=dev)
+            L.scatter_rows_zero_bf16(dz_c, run.cb.inv32, dz)
+        sk = max(2, min(16, dyb.shape[0] // 512))
 
         if site.grouped:
             # dWu += dy^T z, dWd += dz^T x, dbd += colsum(dz) are NOT launched here: one adapter alone has 48 output tiles.
@@ -1434,6 +1497,9 @@ class Engine(LiveSetMixin):
         H, I, dev = self.H, self.I, self.dev
         N = dout.shape[0]
         p = f"deberta.encoder.layer.{li}"
+        cb = run.cb
+        if cb is not None:
+            return self._layer_bwd_compact(run, sv, dout, cb)
         dt2, dy2 = self._ln_bwd(p + ".output.LayerNorm", dout, sv.ln2, run.p_hid, sv.seed_ln2,
                                 dysum=self.Gl.get(a2.name + ".up.bias") if a2 is not None else None)
         df = dy2
@@ -1506,9 +1572,67 @@ class Engine(LiveSetMixin):
         L.gemm(dq_op, W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
         return dq, dkv_op
 
+    def _layer_bwd_compact(self, run, sv: "LayerSave", dout: torch.Tensor, cb: Packing):
+        """_layer_bwd on the compact rows of `cb` (dout [Np, H]; same return values, on compact rows).  Every GEMM and the attention
+        backward are row-independent: they run the same code on fewer rows and give each row the bits the padded pass gives it.
+        What reduces over rows keeps the padded order: the column sums of the LayerNorm backward (fbl_ln_bwd_rows walks the
+        padded rows and skips the ones without a compact row) and the adapter weight gradients (padded operands, _adapter_bwd).
+        One fused gather brings what the compact kernels read from the padded forward onto their rows."""
+        li = sv.li
+        W, (a1, a2) = self.Lw[li], self.sites[li]
+        H, I, dev = self.H, self.I, self.dev
+        Np = dout.shape[0]
+        p = f"deberta.encoder.layer.{li}"
+        pairs = [(t, torch.empty(Np, t.shape[1], dtype=t.dtype, device=dev))
+                 for t in (sv.qkv, sv.ctx, sv.hpre, sv.z1 if a1 is not None else None, sv.z2 if a2 is not None else None) if t is not None]
+        L.gather_rows_multi(pairs, cb.sel32)
+        got = {id(src): dst for src, dst in pairs}
+        qkv, ctx, hpre = got[id(sv.qkv)], got[id(sv.ctx)], got[id(sv.hpre)]
+        dt2, dy2, dy2p = self._ln_bwd(p + ".output.LayerNorm", dout, sv.ln2, run.p_hid, sv.seed_ln2,
+                                      dysum=self.Gl.get(a2.name + ".up.bias") if a2 is not None else None, cb=cb)
+        df = dy2
+        if a2 is not None:
+            df = self._adapter_bwd(run, a2, dy2, got[id(sv.z2)], sv.fb, sv.seed_ad2, pad=(dy2p, sv.z2))
+        del dy2p
+        dh = torch.empty(Np, I, dtype=BF16, device=dev)
+        L.gemm(df, W["WdT"], aux=hpre, aux_kind=L.AUX_MUL_BF16, out_bf16=dh)
+        da = torch.empty(Np, H, dtype=F32, device=dev)
+        L.gemm(dh, W["WiT"], aux=dt2, aux_kind=L.AUX_ADD_F32, out_f32=da)
+        del dh, hpre
+        dctx = torch.empty(Np, H, dtype=BF16, device=dev)
+        if a1 is not None and a1.merged:  # the folded [dy | dz] operand (_layer_bwd), on compact rows
+            A1, Kf = a1.A, a1.WF.shape[1]
+            # its zeroed padding columns: ONE buffer per row count (the dense GEMM below is its last reader: the weight
+            # gradients read the padded copies), not a strided fill per layer execution
+            dyz = self._dyz_compact
+            if dyz is None or tuple(dyz.shape) != (Np, Kf):
+                dyz = self._dyz_compact = torch.zeros(Np, Kf, dtype=BF16, device=dev)
+            dt1, dy1, dy1p = self._ln_bwd(p + ".attention.output.LayerNorm", da, sv.ln1, run.p_hid, sv.seed_ln1,
+                                          dysum=self.Gl.get(a1.name + ".up.bias"), dy_out=dyz[:, :H], cb=cb)
+            self._adapter_bwd(run, a1, dy1, got[id(sv.z1)], sv.ob, sv.seed_ad1, dz_out=dyz[:, H:H + A1], pad=(dy1p, sv.z1))
+            L.gemm(dyz, a1.WF, out_bf16=dctx)
+        else:
+            dt1, dy1, dy1p = self._ln_bwd(p + ".attention.output.LayerNorm", da, sv.ln1, run.p_hid, sv.seed_ln1,
+                                          dysum=self.Gl.get(a1.name + ".up.bias") if a1 is not None else None, cb=cb)
+            do = dy1
+            if a1 is not None:
+                do = self._adapter_bwd(run, a1, dy1, got[id(sv.z1)], sv.ob, sv.seed_ad1, pad=(dy1p, sv.z1))
+            L.gemm(do, W["WoT"], out_bf16=dctx)
+        del dy1p
+        svc = dataclasses.replace(sv, qkv=qkv, ctx=ctx)  # the attention backward reads q / k / v / O on compact rows (row0)
+        dqkv = self._attn_bwd(run, svc, dctx)
+        sv.psave = sv.msave = None
+        if not sv.emd:
+            dx = torch.empty(Np, H, dtype=F32, device=dev)
+            L.gemm(dqkv, W["WqkvT"], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dx)
+            return dx, None
+        dq = torch.empty(Np, H, dtype=F32, device=dev)
+        L.gemm(dqkv[:, :H], W["WqkvT"][:, :H], aux=dt1, aux_kind=L.AUX_ADD_F32, out_f32=dq)
+        return dq, dqkv[:, H:]
+
     def _attn_bwd(self, run, sv, dctx):
         """Backward of the attention of one layer execution on the token rows: the bf16 [dQ | dK | dV] operand [N, 3H]."""
-        dqkv = torch.empty(run.N, 3 * self.H, dtype=BF16, device=self.dev)
+        dqkv = torch.empty(dctx.shape[0], 3 * self.H, dtype=BF16, device=self.dev)
         # The position-table gradients of this execution (dPK = G1^T.Q, dPQ = G2^T.K) are NOT formed here: its dS / dS^T and
         # q / k go on the per-step lists, and one chain at the END of backward handles all executions
         # (attn_bwd.pos_table_grads_batched).  ft_ln=False: nothing trainable sits behind the position tables, nothing is kept.
@@ -1548,10 +1672,11 @@ class Engine(LiveSetMixin):
         dlog[:, :Vout].copy_(g)
         return dlog
 
-    def _head_bwd(self, run, rows, dlog, dq, all_rows=False, compact=False):
+    def _head_bwd(self, run, rows, dlog, dq, all_rows=False, compact=False, to_rows=None):
         """Backward of the prediction head for the rows `rows` (int32 indices into the N token rows) given their bf16
         logit gradients dlog [R, Vp]: dq[rows] += d/d(head input).  Head LayerNorm gradients are accumulated.
-        compact: the forward ran the head on exactly these rows (logit_rows), so what it saved is already [R, .]."""
+        compact: the forward ran the head on exactly these rows (logit_rows), so what it saved is already [R, .].
+        to_rows: the rows of dq that receive the result when dq has another row layout than the forward (compact backward)."""
         H, dev = self.H, self.dev
         R, Vp = dlog.shape
         Vout = run.Vout
@@ -1579,7 +1704,7 @@ class Engine(LiveSetMixin):
         if all_rows:
             dq.add_(dqr)
         else:
-            L.scatter_rows_f32(dqr, rows, dq)  # first contribution: dq is still zero at these rows
+            L.scatter_rows_f32(dqr, rows if to_rows is None else to_rows, dq)  # first contribution: dq is still zero at these rows
 
     def backward(self, run, gloss: Optional[torch.Tensor], glogits: Optional[torch.Tensor] = None, attach: bool = True,
                  ghid=None):
@@ -1622,7 +1747,12 @@ class Engine(LiveSetMixin):
         red = _Ready(self, run, reducer) if reducer is not None else None
         run.dw_pending, run.dw_ready_keys, run.dw_count = [], [], 0
         dec = run.dec_plan  # decoder on selected rows: the head and the decoder work on the R compact rows
-        dq = L.zeros(dec.R if dec is not None else N, H, dtype=F32, device=dev)
+        # The compact backward (_backward_rows made its layout with the forward): from here down to layer 0 on the rows that exist.
+        # Only the loss's own gradient keeps the padding rows at exactly zero: one handed in on the logits or on a hidden state
+        # reaches them, and such a backward stays on the padded grid.
+        cb = run.cb = run.bwd_rows if (glogits is None and ghid is None and gloss is not None and dec is None and pk is None) else None
+        run.bwd_compact = cb is not None
+        dq = L.zeros(dec.R if dec is not None else (cb.n if cb is not None else N), H, dtype=F32, device=dev)
         Vout = run.Vout
         Vp = _ru(Vout, 64)
         # ---- CE + head, on the labelled rows only (all other rows have exactly zero gradient)
@@ -1638,7 +1768,7 @@ class Engine(LiveSetMixin):
                 if dec is not None:
                     self._head_bwd(run, None, dlog, dq, all_rows=True, compact=True)
                 else:
-                    self._head_bwd(run, rows, dlog, dq)
+                    self._head_bwd(run, rows, dlog, dq, to_rows=cb.inv32[rows.long()] if cb is not None else None)
                 del dlog
         # ---- gradient handed in on the logits of the requested rows (logit_rows): the head backward on those R rows only,
         # scatter-added into the zeroed dq at their activation rows (distinct: check_logit_rows)
@@ -1668,10 +1798,17 @@ class Engine(LiveSetMixin):
             run.dw_ready_keys.append(key)
             self._dw_flush(run, red)
 
+        def to_grid(x):
+            """compact backward: fp32 rows back onto the padded grid (zeros where a row has no compact row) -- what follows runs
+            there: the convolution's taps cross row boundaries, the embedding stage ends on the grid"""
+            run.cb = None
+            return L.zeros(N, H, dtype=F32, device=dev).index_copy_(0, cb.sel, x)
+
         def end(dx_emb=None):
             """the tail every backward ends with, wherever its lowest stage is: the parked products, the side stream, the
             position-table chain (all of its executions have run whenever its LayerNorm is live), the embedding stage when it
             runs, and the gradient exchange -- finish() releases the buckets of the stages that did not run"""
+            run.cb = None
             self._dw_flush(run, red, force=True)
             if run.side_used:
                 torch.cuda.current_stream().wait_stream(self.side)  # all adapter dW/db are in the flat grad buffer
@@ -1714,7 +1851,7 @@ class Engine(LiveSetMixin):
             WkvT = self.Lw[self.nL - 1]["WqkvT"][:, H:]
             dx = dq
             for op in dkv_ops:
-                acc = torch.empty(N, H, dtype=F32, device=dev)
+                acc = torch.empty(dx.shape[0], H, dtype=F32, device=dev)
                 L.gemm(op, WkvT, aux=dx, aux_kind=L.AUX_ADD_F32, out_f32=acc)
                 dx = acc
         del dkv_ops
@@ -1738,7 +1875,16 @@ class Engine(LiveSetMixin):
             g = self._hid_grad(run, ghid, sv.li + 1)  # handed in on this layer's output (behind the convolution for layer 0)
             if g is not None:
                 dx.add_(g)
-            if sv.li == 0 and cfg.conv_kernel_size:
+            if sv.li == 0 and cfg.conv_kernel_size and cb is not None:
+                # compact backward: the convolution stage on the padded grid (its dropout is keyed by the padded element, its taps
+                # reach the neighbouring rows), layer 0 on the compact rows in between
+                dx, dcol = self._conv_bwd(run, to_grid(dx))
+                run.cb = cb
+                dx, _ = self._layer_bwd(run, sv, dx.index_select(0, cb.sel))
+                dx = to_grid(dx)
+                L.col2im3(dcol, dx, B, S, H, 1)
+                stage_done("conv")
+            elif sv.li == 0 and cfg.conv_kernel_size:
                 dx, dcol = self._conv_bwd(run, dx)
                 dx, _ = self._layer_bwd(run, sv, dx)
                 if pk is None:
@@ -1762,6 +1908,8 @@ class Engine(LiveSetMixin):
             L.ln_bwd(dx, cn.t, cn.stats, cn.gamma, rowmask=cn.rowmask, dgamma=self.Gl.get("deberta.encoder.conv.LayerNorm.weight"),
                      dbeta=self.Gl.get("deberta.encoder.conv.LayerNorm.bias"), ws=self._ln_ws)
             stage_done("conv")
+        if run.cb is not None:  # (no convolution: the compact rows end here)
+            dx = to_grid(dx)
         return end(dx if runs("emb") else None)
 
     def _backward_bottom(self, run, red, ghid, dx):
@@ -1933,6 +2081,9 @@ class Run:
     want_attn: bool = False                        # output_attentions=True
     seed_word: Optional[torch.Tensor] = None       # device word added to every dropout seed of this pass (see Engine.run)
     pk: Optional["Packing"] = None                 # packed-row layout of this pass (model.packed_rows) or None: the padded [B, S] grid
+    bwd_rows: Optional["Packing"] = None           # the compact layout the BACKWARD may use next to a padded forward (Engine._backward_rows)
+    cb: Optional["Packing"] = None                 # ... set while the backward is on it (_backward: from the head down to layer 0)
+    bwd_compact: bool = False                      # ... whether this step's backward ran on it (set by _backward; tests, tools)
     N: int = 0                                     # activation rows: B*S, or pk.n
     embeds: Optional[torch.Tensor] = None          # inputs_embeds [B, L, H] given in place of input_ids
     P: int = 0                                     # prompt slots between the video slots and the text (S = T + P + Lt)

@@ -70,6 +70,8 @@ LORA_SIGNATURES = _header_signatures("fbl_lora.h")    # LoRA merged into the pac
 EMA_SIGNATURES = _header_signatures("fbl_ema.h")      # the moving average of the trainable weights inside the Adam launch
 PROMPT_SIGNATURES = _header_signatures("fbl_prompt.h")  # prompt tuning: the embedding rows with the prompt slots, its gradient
 
+ROWS_SIGNATURES = _header_signatures("fbl_rows.h")      # the compact row layout of the backward pass: gather / scatter, ln_bwd on it
+
 _LIB = None
 
 
@@ -86,7 +88,8 @@ def load(path: Optional[str] = None):
     lib = C.CDLL(p)
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
                               *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items(),
-                              *LORA_SIGNATURES.items(), *EMA_SIGNATURES.items(), *PROMPT_SIGNATURES.items()):
+                              *LORA_SIGNATURES.items(), *EMA_SIGNATURES.items(), *PROMPT_SIGNATURES.items(),
+                              *ROWS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -797,6 +800,50 @@ def scatter_rows_f32(x, rows, out):
     ld = _rows2d(out, "out")
     _chk(load().fbl_scatter_rows_f32(_p(x), _p(rows), rows.numel(), x.shape[1], _p(out), ld, _stream()),
          "fbl_scatter_rows_f32")
+
+
+# ---- the compact row layout of the backward pass (include/fbl_rows.h)
+GATHER_MAX_TENSORS = 8  # FBL_GATHER_MAX_TENSORS
+
+
+def gather_rows_multi(pairs, sel):
+    """One launch: dst[c] = src[sel[c]] for every (src, dst) of `pairs` (at most GATHER_MAX_TENSORS; 2-D row-major views of one
+    element size each, dst [Np, cols]); sel int32 [Np]."""
+    _req(sel, torch.int32, "sel")
+    Np, n = sel.numel(), len(pairs)
+    assert sel.is_contiguous() and 1 <= n <= GATHER_MAX_TENSORS
+    rb, sl, dl = [], [], []
+    for src, dst in pairs:
+        assert src.dtype == dst.dtype and src.is_cuda and dst.is_cuda and src.shape[1] == dst.shape[1] and dst.shape[0] == Np
+        es = src.element_size()
+        rb.append(src.shape[1] * es); sl.append(_rows2d(src, "src") * es); dl.append(_rows2d(dst, "dst") * es)
+    tab = lambda ts: (C.c_void_p * n)(*[_p(t) for t in ts])
+    arr = lambda v: (C.c_int64 * n)(*v)
+    _chk(load().fbl_gather_rows_multi(n, tab([s for s, _ in pairs]), tab([d for _, d in pairs]), arr(rb), arr(sl), arr(dl), _p(sel),
+                                      Np, _stream()), "fbl_gather_rows_multi")
+
+
+def scatter_rows_zero_bf16(src, inv, out):
+    """out[r] = src[inv[r]] where inv[r] >= 0, zeros elsewhere (bf16; out [N_pad, cols], inv int32 [N_pad])"""
+    _req(src, torch.bfloat16, "src"); _req(out, torch.bfloat16, "out"); _req(inv, torch.int32, "inv")
+    assert inv.is_contiguous() and inv.numel() == out.shape[0] and src.shape[1] == out.shape[1]
+    _chk(load().fbl_scatter_rows_zero_bf16(_p(src), _rows2d(src, "src"), _p(inv), out.shape[0], out.shape[1], _p(out),
+                                           _rows2d(out, "out"), _stream()), "fbl_scatter_rows_zero_bf16")
+
+
+def ln_bwd_rows(dout, inv, t, stats, gamma, *, rowmask=None, p_drop=0.0, seed=0, out_dt=None, out_dy_bf16=None, out_dy_pad,
+                dgamma=None, dbeta=None, dysum=None, ws=None):
+    """ln_bwd with dout / out_dt / out_dy_bf16 on compact rows and t / stats / rowmask / out_dy_pad on the padded rows; inv int32
+    [N_pad]: the compact row of each padded row or -1 (include/fbl_rows.h)."""
+    N, H = t.shape
+    _req(inv, torch.int32, "inv"); _req(out_dy_pad, torch.bfloat16, "out_dy_pad")
+    assert dout.is_contiguous() and t.is_contiguous() and inv.is_contiguous() and inv.numel() == N
+    assert out_dy_pad.is_contiguous() and tuple(out_dy_pad.shape) == (N, H) and dout.shape[1] == H
+    assert out_dt is None or (out_dt.is_contiguous() and out_dt.shape == dout.shape)
+    ld_dyb = _rows2d(out_dy_bf16, "out_dy_bf16") if out_dy_bf16 is not None else 0
+    _chk(load().fbl_ln_bwd_rows(_p(dout), _p(inv), _p(rowmask), _p(t), _p(stats), _p(gamma), float(p_drop), int(seed), _seed_dev(),
+                                _p(out_dt), _p(out_dy_bf16), ld_dyb, _p(out_dy_pad), _p(dgamma), _p(dbeta), _p(dysum), _p(ws), N, H,
+                                _stream()), "fbl_ln_bwd_rows")
 
 
 _SUMSQ_WS = {}

@@ -310,6 +310,10 @@ class DebertaV2ForMaskedLM(nn.Module):
         self.packed_rows = False
         # opt-in: the two enhanced-mask-decoder passes, the head and their backward on the selected rows only (engine.py)
         self.decoder_rows = False
+        # the compact backward (Engine._backward_rows): the padded step's backward on the rows that exist, same gradient bits.
+        # None: the engine's rule decides per batch; False: always the padded backward (A/B runs); True: the rule without its
+        # share threshold (tests)
+        self.compact_backward = None
         # opt-in, read per call: an int k in 1..16 makes every call return `predictions` (predict.Predictions) -- top-k ids and
         # log-probabilities of the rows the call forms logits for anyway (the labelled rows, the `logit_rows`, else every row),
         # with the label's rank and the row's NLL on a labelled call.  One extra pass over those [R, V] logits; never fills the
