@@ -44,7 +44,7 @@ def sources():
 
 def _deps_mtime() -> float:
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("fbl.h", "fbl_mha.h", "fbl_qrows.h", "fbl_live.h", "fbl_predict.h", "fbl_groups.h", "fbl_lora.h", "fbl_ema.h", "fbl_prompt.h", "fbl_rows.h")]
+    hdrs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("fbl.h", "fbl_mha.h", "fbl_qrows.h", "fbl_live.h", "fbl_predict.h", "fbl_groups.h", "fbl_lora.h", "fbl_ema.h", "fbl_prompt.h", "fbl_rows.h", "fbl_prompt_layers.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -22,7 +22,7 @@ from . import lib as L
 from .predict import check_topk, of_call as predictions_of_call
 from .live_set import REL_LN, LiveSetMixin, flat_layout, stage_plan
 from .attn_bwd import ATTN_SCALE, _relidx_range, disent_attn_bwd, pos_chain_buffers, pos_table_grads_batched
-from .model.deberta import PROMPT_NAME
+from .model.deberta import PROMPT_NAME, layer_prompt_name
 from .model.relpos import rel_index_vector
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -174,6 +174,8 @@ class Engine(LiveSetMixin):
         #   dw_group       adapter gradient products per launch (<= 16)
         self.dw_group = max(1, min(L.ADW_MAX_ADAPTERS, int(o.get("dw_group", 16))))
         self.n_prompt = int(getattr(model, "n_prompt", 0))  # prompt tuning: trainable embedding rows in front of the text
+        # deep prompt tuning: layers 1 .. prompt_depth-1 read their own rows in the prompt slots of their input (_prompt_overwrite)
+        self.prompt_depth = int(getattr(model, "prompt_depth", 1))
         self._build_flat()
         self._pack_frozen()
         self._build_trainable_operands()
@@ -1104,6 +1106,8 @@ class Engine(LiveSetMixin):
                 x = self._conv_fwd(run, emb, x)
                 if not (run.save and self._stage_runs(run, "conv")):
                     run.conv_c = run.conv_norm = None
+            if 1 <= i + 1 < self.prompt_depth:  # deep prompt tuning: layer i+1 has prompt rows of its own
+                x = self._prompt_overwrite(run, i + 1, x)
             hs.append(x)
         if not (run.save and self._stage_runs(run, "emb")):
             run.emb_norm = run.video_bf16 = None
@@ -1338,6 +1342,20 @@ class Engine(LiveSetMixin):
             if out_bf16 is not None:
                 out_bf16.copy_(v)
         return out_f32
+
+    def _prompt_overwrite(self, run, i: int, x: Stream) -> Stream:
+        """Deep prompt tuning: hs[i], the input of layer i (1 <= i < prompt_depth), with that layer's prompt rows in the prompt
+        slots of every sample.  A normalised stream cannot express an overwritten row, so hs[i] becomes a materialised fp32
+        stream with a bf16 operand copy of its own (norm=None, the form the embedding stream has behind its dropout): the rows
+        are the parameter's fp32 bits -- no LayerNorm, mask or dropout -- and their one rounding to bf16.  What layer i-1 saved
+        for its backward (its LayerNorm's pre-norm tensor and statistics) is not touched: that LayerNorm ran on the real values
+        and receives zero gradient rows at the slots (_backward)."""
+        N, H = run.N, self.H
+        f32 = torch.empty(N, H, dtype=F32, device=self.dev)
+        full = torch.empty(N + self.span2, H, dtype=BF16, device=self.dev)
+        self._materialize(x, out_f32=f32, out_bf16=full[:N])
+        L.prompt_rows_write(self.P[layer_prompt_name(i)], run.row0, run.B, run.S, run.T, out_f32=f32, out_bf16=full[:N])
+        return Stream(bf16=full[:N], plain=f32, full=full)
 
     def _conv_fwd(self, run, emb: Stream, l0: Stream) -> Stream:
         """ConvLayer (:395-419): LN(l0 + gelu(drop(mask * conv1d_k3(emb)))) * mask, conv as a K=3H GEMM on an im2col."""
@@ -1798,6 +1816,18 @@ class Engine(LiveSetMixin):
             run.dw_ready_keys.append(key)
             self._dw_flush(run, red)
 
+        D = self.prompt_depth
+
+        def prompt_rows(i, dx):
+            """deep prompt tuning: dx becomes the complete gradient of hs[i] (1 <= i < D) -- what the caller handed in on
+            hidden_states[i] joins here, not one stage further down -- its prompt slots' rows, summed over the batch in ascending
+            b, are the gradient of layer i's prompt (nothing is summed for a frozen one), and are then cleared: everything
+            upstream of the overwrite receives exactly zero from them (fbl_prompt_rows_grad)"""
+            g = self._hid_grad(run, ghid, i)
+            if g is not None:
+                dx.add_(g)
+            L.prompt_rows_grad(dx, run.row0, B, S, T, run.P, self.Gl.get(layer_prompt_name(i)))
+
         def to_grid(x):
             """compact backward: fp32 rows back onto the padded grid (zeros where a row has no compact row) -- what follows runs
             there: the convolution's taps cross row boundaries, the embedding stage ends on the grid"""
@@ -1846,8 +1876,10 @@ class Engine(LiveSetMixin):
         # gradients [dK | dV] . [Wk ; Wv] -- accumulated by the epilogues of those two GEMMs
         # (the decoder is the lowest stage that runs: nothing below asks for the gradient of hs[-2], it is not formed)
         below = run.plan is None or run.plan.lowest < run.plan.stages.index("decoder")
+        # (deep prompt tuning down to the last layer: its prompt's gradient is the slots' rows of the gradient of hs[-2])
+        top_prompt = D == self.nL and D > 1
         dx = None
-        if below:
+        if below or (top_prompt and layer_prompt_name(self.nL - 1) in self.Gl):
             WkvT = self.Lw[self.nL - 1]["WqkvT"][:, H:]
             dx = dq
             for op in dkv_ops:
@@ -1866,13 +1898,16 @@ class Engine(LiveSetMixin):
                     dx.add_(dxe)
                 del dxe
             del sv
+        if top_prompt and dx is not None:
+            prompt_rows(self.nL - 1, dx)
         stage_done(f"layer{self.nL - 1}")
         if not below:
             return end()
         # ---- encoder layers nL-2 .. 0
         while layers:
             sv = layers.pop()
-            g = self._hid_grad(run, ghid, sv.li + 1)  # handed in on this layer's output (behind the convolution for layer 0)
+            # handed in on this layer's output (behind the convolution for layer 0); a boundary with prompt rows took it already
+            g = self._hid_grad(run, ghid, sv.li + 1) if not 1 <= sv.li + 1 < D else None
             if g is not None:
                 dx.add_(g)
             if sv.li == 0 and cfg.conv_kernel_size and cb is not None:
@@ -1898,10 +1933,12 @@ class Engine(LiveSetMixin):
                 stage_done("conv")
             else:
                 dx, _ = self._layer_bwd(run, sv, dx)
+            if 1 <= sv.li < D:
+                prompt_rows(sv.li, dx)
             stage_done(f"layer{sv.li}")
         if cfg.conv_kernel_size and runs("conv") and not runs("layer0"):
             # the conv stage is the lowest that runs (layer 0 was not saved): only its LayerNorm's gamma / beta are wanted
-            g = self._hid_grad(run, ghid, 1)
+            g = self._hid_grad(run, ghid, 1) if D < 2 else None  # (D >= 2: joined at layer 1's prompt rows)
             if g is not None:
                 dx.add_(g)
             cn = run.conv_norm

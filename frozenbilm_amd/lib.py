@@ -71,6 +71,7 @@ EMA_SIGNATURES = _header_signatures("fbl_ema.h")      # the moving average of th
 PROMPT_SIGNATURES = _header_signatures("fbl_prompt.h")  # prompt tuning: the embedding rows with the prompt slots, its gradient
 
 ROWS_SIGNATURES = _header_signatures("fbl_rows.h")      # the compact row layout of the backward pass: gather / scatter, ln_bwd on it
+PROMPT_LAYERS_SIGNATURES = _header_signatures("fbl_prompt_layers.h")  # deep prompt tuning: per-layer prompt rows, their gradient
 
 _LIB = None
 
@@ -89,7 +90,7 @@ def load(path: Optional[str] = None):
     for name, (res, args) in (*SIGNATURES.items(), *MHA_SIGNATURES.items(), *QROWS_SIGNATURES.items(),
                               *LIVE_SIGNATURES.items(), *PREDICT_SIGNATURES.items(), *GROUP_SIGNATURES.items(),
                               *LORA_SIGNATURES.items(), *EMA_SIGNATURES.items(), *PROMPT_SIGNATURES.items(),
-                              *ROWS_SIGNATURES.items()):
+                              *ROWS_SIGNATURES.items(), *PROMPT_LAYERS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -426,6 +427,43 @@ def prompt_grad(dt, row0, B, S, T, g):
     else:
         assert dt.shape[0] >= B * S
     _chk(load().fbl_prompt_grad(_p(dt), _p(row0), B, S, T, P, H, _p(g), _stream()), "fbl_prompt_grad")
+
+
+def _prompt_rows_checks(t, row0, B, S, T, P, H, what):
+    assert t.is_contiguous() and t.dim() == 2 and t.shape[1] == H, (what, tuple(t.shape), H)
+    if row0 is not None:
+        _req(row0, torch.int32, "row0")
+        assert row0.is_contiguous() and row0.numel() >= B
+    else:
+        assert S >= T + P and t.shape[0] >= B * S, (what, tuple(t.shape), B, S, T, P)
+
+
+def prompt_rows_write(prompt, row0, B, S, T, out_f32=None, out_bf16=None):
+    """rows (row0[b] if row0 is given else b*S) + T + p of out_f32 / out_bf16 [rows, H] <- prompt[p] (its fp32 bits / its bf16
+    rounding) for every sample b (include/fbl_prompt_layers.h); every other row keeps its value"""
+    P, H = prompt.shape
+    _req(prompt, torch.float32, "prompt")
+    assert prompt.is_contiguous() and (out_f32 is not None or out_bf16 is not None)
+    if out_f32 is not None:
+        _req(out_f32, torch.float32, "out_f32")
+        _prompt_rows_checks(out_f32, row0, B, S, T, P, H, "out_f32")
+    if out_bf16 is not None:
+        _req(out_bf16, torch.bfloat16, "out_bf16")
+        _prompt_rows_checks(out_bf16, row0, B, S, T, P, H, "out_bf16")
+    _chk(load().fbl_prompt_rows_write(_p(prompt), _p(row0), B, S, T, P, H, _p(out_f32), _p(out_bf16), _stream()),
+         "fbl_prompt_rows_write")
+
+
+def prompt_rows_grad(dx, row0, B, S, T, P, g):
+    """g [P, H] += sum over the samples, in ascending b, of dx[(row0[b] if row0 is given else b*S) + T + p]; those rows of dx
+    are then zero (include/fbl_prompt_layers.h).  g None (a frozen prompt): the rows are cleared only."""
+    H = dx.shape[1]
+    _req(dx, torch.float32, "dx")
+    _prompt_rows_checks(dx, row0, B, S, T, P, H, "dx")
+    if g is not None:
+        _req(g, torch.float32, "g")
+        assert g.is_contiguous() and tuple(g.shape) == (P, H), (tuple(g.shape), P, H)
+    _chk(load().fbl_prompt_rows_grad(_p(dx), _p(row0), B, S, T, P, H, _p(g), _stream()), "fbl_prompt_rows_grad")
 
 
 def ln_fwd(*, y=None, p_drop=0.0, seed=0, r_plain=None, r_norm=None, gamma, beta, eps, rowmask=None, out_t=None,

@@ -34,6 +34,7 @@ def build_model(args, config=None):
             lora_alpha=getattr(args, "lora_alpha", None),
             lora_targets=getattr(args, "lora_targets", LORA_DEFAULT_TARGETS),
             n_prompt=getattr(args, "n_prompt", 0),
+            prompt_depth=getattr(args, "prompt_depth", 1),
         )
     if "deberta" not in name:
         raise NotImplementedError(f"only the DeBERTa-v2 and BERT paths are implemented (model_name={name!r})")
@@ -54,6 +55,7 @@ def build_model(args, config=None):
         lora_alpha=getattr(args, "lora_alpha", None),
         lora_targets=getattr(args, "lora_targets", LORA_DEFAULT_TARGETS),
         n_prompt=getattr(args, "n_prompt", 0),
+        prompt_depth=getattr(args, "prompt_depth", 1),
     )
 
 

@@ -93,8 +93,11 @@ def param_shapes(cfg: BertConfig, features_dim: int, n_ans: int):
 
 class BertForMaskedLM(nn.Module):
     def __init__(self, config, features_dim=768, max_feats=10, freeze_lm=True, ft_ln=True, freeze_mlm=True, n_ans=0,
-                 freeze_last=True, lora_rank=0, lora_alpha=None, lora_targets=("query_proj", "value_proj"), n_prompt=0):
+                 freeze_last=True, lora_rank=0, lora_alpha=None, lora_targets=("query_proj", "value_proj"), n_prompt=0,
+                 prompt_depth=1):
         super().__init__()
+        if prompt_depth != 1:
+            raise NotImplementedError("deep prompt tuning (prompt_depth > 1) is implemented for the DeBERTa model only")
         if n_prompt:
             raise NotImplementedError("prompt tuning (n_prompt > 0) is implemented for the DeBERTa model only: the prompt slots "
                                       "would shift the absolute position rows of the text")

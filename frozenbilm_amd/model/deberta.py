@@ -202,6 +202,20 @@ def check_n_prompt(n_prompt) -> int:
     return n_prompt
 
 
+def layer_prompt_name(i: int) -> str:
+    """deep prompt tuning: the prompt rows that encoder layer i >= 1 reads in the prompt slots of its input"""
+    return f"deberta.encoder.layer.{i}.prompt.weight"
+
+
+def check_prompt_depth(prompt_depth, n_prompt: int, n_layers: int) -> int:
+    """the number of stages with prompt rows of their own (the embeddings, then layers 1 .. depth-1), or ValueError"""
+    if isinstance(prompt_depth, bool) or not isinstance(prompt_depth, int) or not 1 <= prompt_depth <= n_layers:
+        raise ValueError(f"prompt_depth must be an integer in 1..num_hidden_layers={n_layers} (got {prompt_depth!r})")
+    if prompt_depth > 1 and not n_prompt:
+        raise ValueError(f"prompt_depth={prompt_depth} needs prompt slots: n_prompt > 0")
+    return prompt_depth
+
+
 def flat_order(cfg: DebertaV2Config, names: List[str]) -> List[str]:
     """Trainable names in backward-completion order (bucket order of the gradient all-reduce)."""
     def take(prefix):
@@ -237,6 +251,7 @@ class DebertaV2ForMaskedLM(nn.Module):
         lora_alpha=None,
         lora_targets=LORA_DEFAULT_TARGETS,
         n_prompt=0,
+        prompt_depth=1,
     ):
         super().__init__()
         # prompt tuning (an extension): n_prompt trainable embedding rows between the video slots and the text of every sample
@@ -248,6 +263,9 @@ class DebertaV2ForMaskedLM(nn.Module):
         self.config = DebertaV2Config.from_any(config)
         self.config.validate_supported()
         cfg = self.config
+        # deep prompt tuning (an extension): layers 1 .. prompt_depth-1 read rows of their own in the prompt slots of their input
+        # (engine.Engine._prompt_overwrite); 1 is the shallow prompt, whose rows enter at the embeddings only
+        self.prompt_depth = check_prompt_depth(prompt_depth, self.n_prompt, cfg.num_hidden_layers)
         for ds in (ds_factor_attn, ds_factor_ff):
             if ds:
                 assert not cfg.hidden_size % ds  # model/adapter.py:10
@@ -291,6 +309,11 @@ class DebertaV2ForMaskedLM(nn.Module):
             g3 = torch.Generator().manual_seed(2)
             t = torch.randn((self.n_prompt, cfg.hidden_size), generator=g3) * cfg.initializer_range
             self._register(PROMPT_NAME, nn.Parameter(t, requires_grad=True))
+        if self.prompt_depth > 1:  # the layers' prompts, layer 1 first, from one more generator: prompt_depth = 1 draws nothing
+            g4 = torch.Generator().manual_seed(3)
+            for i in range(1, self.prompt_depth):
+                t = torch.randn((self.n_prompt, cfg.hidden_size), generator=g4) * cfg.initializer_range
+                self._register(layer_prompt_name(i), nn.Parameter(t, requires_grad=True))
         emb = self._module("deberta.embeddings")
         emb.register_buffer("position_ids", torch.arange(cfg.max_position_embeddings).expand((1, -1)))
         self._engine = None
@@ -344,6 +367,8 @@ class DebertaV2ForMaskedLM(nn.Module):
         if name.startswith("answer_"):
             return not self.freeze_last
         if "linear_video" in name or "adapter" in name or ".lora_" in name or name == PROMPT_NAME:
+            return True
+        if name.startswith("deberta.encoder.layer.") and name.endswith(".prompt.weight"):
             return True
         return bool(self.ft_ln and "LayerNorm" in name)
 
@@ -450,6 +475,32 @@ class DebertaV2ForMaskedLM(nn.Module):
         if int(ids.min()) < 0 or int(ids.max()) >= E.shape[0]:
             raise ValueError(f"ids outside the vocabulary 0..{E.shape[0] - 1}")
         self.get_param(PROMPT_NAME).data.copy_(E.data[ids.to(E.device)])
+        self.invalidate()
+        return self
+
+    def layer_prompt_names(self) -> List[str]:
+        """the parameters of deep prompt tuning, layer 1 first (empty for prompt_depth = 1)"""
+        return [layer_prompt_name(i) for i in range(1, self.prompt_depth)]
+
+    @torch.no_grad()
+    def init_prompt_layers_from_hidden(self, hidden_states, T):
+        """Start deep prompt tuning near the shallow model: layer i's prompt rows <- the batch mean of
+        hidden_states[i][:, T:T+n_prompt] for i = 1 .. prompt_depth-1.  hidden_states: the tuple of an
+        output_hidden_states=True call ([B, S, H] each, S = T + n_prompt + text); T: its number of video slots."""
+        if self.prompt_depth < 2:
+            raise RuntimeError("init_prompt_layers_from_hidden needs a model built with prompt_depth > 1")
+        P, H = self.n_prompt, self.config.hidden_size
+        if isinstance(T, bool) or not isinstance(T, int) or T < 0:
+            raise ValueError(f"T must be a non-negative integer (got {T!r})")
+        if len(hidden_states) < self.prompt_depth:
+            raise ValueError(f"hidden_states holds {len(hidden_states)} tensors, prompt_depth={self.prompt_depth} needs the first "
+                             f"{self.prompt_depth}")
+        for i in range(1, self.prompt_depth):
+            h = hidden_states[i]
+            if h.dim() != 3 or h.shape[0] < 1 or h.shape[1] < T + P or h.shape[2] != H:
+                raise ValueError(f"hidden_states[{i}] must be [batch, at least T + n_prompt = {T + P}, {H}] (got {tuple(h.shape)})")
+            w = self.get_param(layer_prompt_name(i))
+            w.data.copy_(h[:, T:T + P].detach().to(torch.float32).mean(0))
         self.invalidate()
         return self
 

@@ -1,6 +1,6 @@
 """Device-event timings of prompt tuning (`n_prompt`, include/fbl_prompt.h); one JSON object.
 
-    python tools/bench_prompt.py [--steps K] [--warmup W] [--layers N] [--prompt P] [--out FILE] [--p0-only]
+    python tools/bench_prompt.py [--steps K] [--warmup W] [--layers N] [--prompt P] [--prompt-depth D [D ...]] [--out FILE] [--p0-only]
 
 BASELINE config 2 (DeBERTa-v2-XLarge + adapters, B = 32, 10 video slots, 256 text tokens), a model without a prompt and a model
 with P = 20 prompt slots side by side in one process, the legs alternating (rows 32 x 266 against 32 x 286):
@@ -8,6 +8,10 @@ with P = 20 prompt slots side by side in one process, the legs alternating (rows
 1. the MLM training step: forward with labels, backward, clipped FusedAdam, train mode;
 2. the two kernels alone at that shape -- fbl_embed_assemble beside fbl_embed_gather (the P = 0 launch it stands in for) and
    beside the torch imitation (gather, expand, concatenate); fbl_prompt_grad beside the torch slice + sum.
+
+--prompt-depth: one model with P prompt slots per depth given (1: the shallow prompt; D > 1: layers 1 .. D-1 read prompt rows of
+their own, include/fbl_prompt_layers.h), all legs alternating; with a depth above 1 the row kernels of a deep layer are timed too:
+the materialise of its input stream, fbl_prompt_rows_write and fbl_prompt_rows_grad.
 
 --p0-only: the P = 0 leg alone, through a constructor call without the argument -- the same file runs on a tree that predates
 it, for the comparison of the default path with the parent commit (run the two trees in turn, several times each).
@@ -29,6 +33,7 @@ ap.add_argument("--steps", type=int, default=20, help="timed iterations per leg 
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--layers", type=int, default=0, help="encoder layers (0: the xlarge model's 24)")
 ap.add_argument("--prompt", type=int, default=20)
+ap.add_argument("--prompt-depth", type=int, nargs="+", default=[1], help="prompt_depth of the legs with a prompt (one model each)")
 ap.add_argument("--p0-only", action="store_true")
 ap.add_argument("--out", default=None, help="also write the JSON object to this file")
 a = ap.parse_args()
@@ -63,17 +68,22 @@ B, T, Lt, P = 32, 10, 256, a.prompt
 batch = Bn.synth_batch(B, T, 1024, Lt, cfg.vocab_size, seed=1, device=dev)
 
 
-def make(n_prompt):
+def make(n_prompt, depth=1):
     torch.manual_seed(0)
     kw = dict(n_prompt=n_prompt) if n_prompt else {}
+    if depth != 1:
+        kw["prompt_depth"] = depth
     m = DebertaV2ForMaskedLM(cfg, max_feats=10, features_dim=1024, ds_factor_attn=8, ds_factor_ff=8, dropout=0.1, **kw)
     m.to(dev).train()
     return m, FusedAdam(m, lr=3e-5, betas=(0.9, 0.95))
 
 
 models = {"p0": make(0)}
+leg = lambda d: f"p{P}" if d == 1 else f"p{P}d{d}"  # noqa: E731
+first = leg(a.prompt_depth[0])
 if not a.p0_only:
-    models[f"p{P}"] = make(P)
+    for d in a.prompt_depth:
+        models[leg(d)] = make(P, d)
 
 
 def train_step(m, opt):
@@ -86,17 +96,19 @@ def train_step(m, opt):
 out = {"device": torch.cuda.get_device_name(0),
        "method": f"device events; the legs of a group alternate inside one process; median, 10th and 90th percentile of {a.steps} "
                  f"timed iterations after {a.warmup} warm-up iterations",
-       "shape": dict(samples=B, video_slots=T, text=Lt, prompt=0 if a.p0_only else P, layers=cfg.num_hidden_layers,
+       "shape": dict(samples=B, video_slots=T, text=Lt, prompt=0 if a.p0_only else P, prompt_depth=[] if a.p0_only else a.prompt_depth, layers=cfg.num_hidden_layers,
                      rows={k: B * (T + Lt + (0 if k == "p0" else P)) for k in models})}
 out["train_step_ms"] = alternate_stats({k: (lambda mo=mo: train_step(*mo)) for k, mo in models.items()}, a.steps, a.warmup)
 if not a.p0_only:
     from frozenbilm_amd import lib as L
 
     tr = out["train_step_ms"]
-    out["train_overhead_ms"] = round(tr[f"p{P}"]["median"] - tr["p0"]["median"], 3)
+    out["train_overhead_ms"] = {k: round(v["median"] - tr["p0"]["median"], 3) for k, v in tr.items() if k != "p0"}
+    if len(out["train_overhead_ms"]) == 1:
+        out["train_overhead_ms"] = out["train_overhead_ms"][first]
     out["train_ms_per_1000_rows"] = {k: round(v["median"] / out["shape"]["rows"][k] * 1000, 3) for k, v in tr.items()}
     H, S = cfg.hidden_size, T + P + Lt
-    eng = models[f"p{P}"][0].engine()
+    eng = models[first][0].engine()
     ids, E, prompt = batch["input_ids"].contiguous(), eng.E32, eng.P["deberta.embeddings.prompt_embeddings.weight"]
     vproj = torch.randn(B * T, H, device=dev)
     t_new, t_old = torch.empty(B, S, H, device=dev), torch.empty(B * (T + Lt), H, device=dev)
@@ -109,6 +121,18 @@ if not a.p0_only:
         "torch_slice_sum": lambda: g.add_(dt0.view(B, S, H)[:, T:T + P].sum(0)),
     }, max(a.steps, 50), a.warmup)
     out["kernel_bytes"] = dict(embed_assemble=2 * B * S * H * 4, prompt_grad=(B + 2) * P * H * 4)
+    if max(a.prompt_depth) > 1:  # the row kernels one deep layer adds to a step, at this shape
+        n = eng.P["deberta.encoder.layer.0.output.LayerNorm.weight"]
+        t_, stats = torch.randn(B * S, H, device=dev), torch.stack([torch.zeros(B * S, device=dev), torch.ones(B * S, device=dev)], 1)
+        f32, b16 = torch.empty(B * S, H, device=dev), torch.empty(B * S, H, dtype=torch.bfloat16, device=dev)
+        dx = torch.randn(B * S, H, device=dev)
+        out["deep_layer_kernels_ms"] = alternate_stats({
+            "fbl_ln_materialize": lambda: L.ln_materialize(t_, stats.contiguous(), n, n, out_f32=f32, out_bf16=b16),
+            "fbl_prompt_rows_write": lambda: L.prompt_rows_write(prompt, None, B, S, T, out_f32=f32, out_bf16=b16),
+            "fbl_prompt_rows_grad": lambda: L.prompt_rows_grad(dx, None, B, S, T, P, g),
+        }, max(a.steps, 50), a.warmup)
+        out["deep_layer_kernel_bytes"] = dict(ln_materialize=B * S * H * (4 + 4 + 2), prompt_rows_write=B * P * H * (4 + 2) + P * H * 4,
+                                              prompt_rows_grad=(2 * B + 2) * P * H * 4)
 print(json.dumps(out))
 if a.out:
     with open(a.out, "w") as f:
